@@ -12,6 +12,10 @@ all-reduce between the local per-tensor clip and Adam, the CrossShardOptimizer o
 `python -m torch.distributed.run`; this parent never touches a GPU) and relays rank 0's JSON line as its last
 line of stdout.  Rank 0 prints ONE JSON line.  The step is captured once into HIP graphs (torch.cuda.CUDAGraph)
 and replayed, or launched eagerly, whichever an untimed probe finds faster.
+
+A plain run sets up, warms up, times --steps steps and prints the line.  --full adds what takes runs of its own after
+the timed region: the per-kernel HIP-event table and roofline (`roofline`) and the CPU stand-ins (`cpu_baseline`).
+--dump-outputs DIR writes what the last timed step computed (loss, logits, updated parameters) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -354,12 +358,14 @@ class StepForms:
         self.loss_buf = torch.zeros(1, device=dev)
         self.audio_buf = torch.zeros(1, device=dev)
         self.graphs = []
+        self.logits = None              # logits of the last eagerly launched step (what LasModel.train_step keeps, too)
+        self.graph_logits = {}          # 'plain' / 'overlap' -> the logits a replay of that form's graphs writes
 
     # -- the plain step ------------------------------------------------------------------------------------------------------
     def part_a(self):     # zero grads, forward, loss, backward, L2 term + per-tensor norms (+ clip before the all-reduce)
         model = self.model
         model.vars.grad.zero_()
-        audio, _, dlogits = model.forward_train(self.feats, self.labels, num_steps=self.U)
+        audio, self.logits, dlogits = model.forward_train(self.feats, self.labels, num_steps=self.U)
         if self.multi:
             model.backward(dlogits)
             model.collect_status(zero_norms=True)   # timeout flag of the persistent kernels: travels with the gradients, gates Adam
@@ -392,7 +398,7 @@ class StepForms:
     def part_a1(self):
         model = self.model
         model.vars.grad.zero_()
-        audio, _, dlogits = model.forward_train(self.feats, self.labels, num_steps=self.U)
+        audio, self.logits, dlogits = model.forward_train(self.feats, self.labels, num_steps=self.U)
         self.audio_buf.copy_(audio)
         model.backward_exchange_begin(dlogits, exchange=False)
 
@@ -452,6 +458,7 @@ class StepForms:
                 g1, g2, g3 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g1):
                     self.part_a1()
+                self.graph_logits['overlap'] = self.logits
                 with torch.cuda.graph(g2, pool=g1.pool()):
                     self.part_a2()
                 with torch.cuda.graph(g3, pool=g1.pool()):
@@ -466,6 +473,7 @@ class StepForms:
                 ga, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
                 with torch.cuda.graph(ga):
                     self.part_a()
+                self.graph_logits['plain'] = self.logits
                 with torch.cuda.graph(gb):
                     self.part_b()
                 self.graphs += [ga, gb]
@@ -510,16 +518,63 @@ def self_launch(argv, gpus):
     return rc if rc else (0 if last_json is not None else 1)
 
 
-def main():
+DUMP_BYTES = 64 * 10 ** 6       # --dump-outputs: at most this many bytes in all (64 MB)
+
+
+def dump_outputs(outputs, out_dir, budget=DUMP_BYTES, seed=0):
+    """Writes {name: tensor or array} as out_dir/<name>.npy, float64 as float64 and everything else as float32.  Arrays that
+    do not fit their share of `budget` are replaced by a fixed, seeded sample of their flattened elements (in index order;
+    the sample depends only on the array's size and its share), so that the files of two runs or two builds compare element
+    for element.  Returns {name: [elements written, elements in the output]}."""
+    import numpy as np
+    arrays = {}
+    for name, v in outputs.items():
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu()
+            v = v.numpy() if v.dtype == torch.float64 else v.float().numpy()
+        a = np.asarray(v)
+        arrays[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    left = budget - 1024 * len(arrays)          # (room for the .npy headers)
+    written = {}
+    for i, name in enumerate(sorted(arrays, key=lambda n: (arrays[n].nbytes, n))):
+        a = arrays[name]
+        share = left // (len(arrays) - i)
+        if a.nbytes > share:
+            k = share // a.itemsize
+            a = a.reshape(-1)[np.sort(np.random.default_rng(seed).choice(a.size, k, replace=False))]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        left -= a.nbytes
+        written[name] = [int(a.size), int(arrays[name].size)]
+    return written
+
+
+def step_outputs(model, forms, used_graph, used_overlap):
+    """What a caller of the timed step receives after its last run: the loss (audio loss + L2 term), the first decoder's logits
+    [B, U, V] (without the vocabulary padding) and the updated parameters (every tensor at its logical shape, flattened and
+    concatenated in the order of the parameter table)."""
+    logits = forms.graph_logits['overlap' if used_overlap else 'plain'] if used_graph else forms.logits
+    V = getattr(model.speller, 'V', logits.shape[-1])
+    params = torch.cat([t.reshape(-1) for t in model.vars.logical('params').values()])
+    return {'loss': forms.loss_buf, 'logits': logits[..., :V], 'params': params}
+
+
+def arg_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also run the per-kernel timing pass (`roofline`) and, with one GPU, the CPU '
+                         'stand-ins of the reference (`cpu_baseline`)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the loss, logits and updated parameters of the last timed step as DIR/<name>.npy (float32, '
+                         'at most 64 MB in all: a fixed sample of a larger output)')
     ap.add_argument('--config', default='metric-M', choices=sorted(CONFIGS))
     ap.add_argument('--no-graph', action='store_true', help='launch eagerly instead of replaying HIP graphs')
     ap.add_argument('--launch', default='auto', choices=['auto', 'graph'],
                     help="auto: an untimed probe picks graph replay or eager launches, whichever is faster; graph: always replay")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU stand-ins')
     ap.add_argument('--dp-overlap', nargs='?', const='on', default='auto', choices=['auto', 'on', 'off'],
                     help="gradient exchange in two buckets, the first one beside the lower layers' backward.  auto (default): "
                          "with more than one rank an untimed probe picks the faster of the overlapped and the plain exchange; "
@@ -527,7 +582,11 @@ def main():
     ap.add_argument('--dp-test-group', action='store_true',
                     help='--gpus 1 only: run the multi-rank code path (clip, all-reduce, Adam; the overlap probe) on a 1-rank RCCL group')
     ap.add_argument('--cpu-sample', type=int, default=16)
-    args = ap.parse_args()
+    return ap
+
+
+def main():
+    args = arg_parser().parse_args()
     c = CONFIGS[args.config]
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
@@ -625,6 +684,9 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
     final_loss = float(loss_buf.item())
+    if args.dump_outputs and rank == 0:     # (before anything else runs a step: --full's timing pass trains on)
+        written = dump_outputs(step_outputs(model, forms, used_graph, used_overlap), args.dump_outputs)
+        print('bench.py: outputs of the last timed step in %s: %s' % (args.dump_outputs, written), file=sys.stderr)
 
     eager = candidates.get('overlap_eager' if used_overlap else 'plain_eager')
     if eager is None:
@@ -660,9 +722,10 @@ def epilogue(rank, world, dt, final_loss, bad_status, eager_step, c, args, confi
     """What every rank does after the timed region; returns (JSON record on rank 0 else None, exit code).
     Anything that invalidates the number -- a bounded-wait timeout of a persistent kernel during the timed steps (Adam was
     withheld on them), a non-finite loss -- is reported IN the record (field `error`) and through the exit code; the record
-    is produced either way.  The per-kernel timing pass (the same step launched eagerly with HIP events around every launch,
-    after the timed region so that `value` is not perturbed) contains the gradient all-reduce when there are several ranks,
-    so EVERY rank runs it (rank 0 alone waited for peers that had already left); only rank 0 builds the record."""
+    is produced either way.  With --full: the per-kernel timing pass (the same step launched eagerly with HIP events around
+    every launch, after the timed region so that `value` is not perturbed) contains the gradient all-reduce when there are
+    several ranks, so EVERY rank runs it (rank 0 alone waited for peers that had already left), and the CPU
+    stand-ins run on a single rank; only rank 0 builds the record."""
     import math
     errors = []
     if any_rank(bool(bad_status)):
@@ -670,38 +733,40 @@ def epilogue(rank, world, dt, final_loss, bad_status, eager_step, c, args, confi
                       'Adam was withheld on those steps' % (bad_status, rank))
     if any_rank(not math.isfinite(final_loss)):
         errors.append('final_loss is not finite (%r on rank %d)' % (final_loss, rank))
-    kernels = (table_fn or kernel_table)(eager_step, c)
-    barrier()
+    if args.full:
+        kernels = (table_fn or kernel_table)(eager_step, c)
+        barrier()
     rc = 1 if errors else 0
     if rank != 0:
         return None, rc
     ms = dt / args.steps * 1e3
     utt_s = c['B'] * world * args.steps / dt
-    f_in, f_rec = lstm_gemm_flops_per_utt(c)
-    dom = kernels[0]         # the dominant kernel = the family with the largest time per step
-    # the committed PMC passes are of the default configuration's step: another configuration's kernels (other unit
-    # counts, other shapes) have no counter evidence and say so
-    traffic, traffic_src, traffic_stale = pmc_traffic(dom['family']) if args.config == 'metric-M' else (None, None, None)
-    step_tflops = 3 * (f_in + f_rec) * utt_s / world / 1e12
     config = dict(config, final_loss=round(final_loss, 4) if math.isfinite(final_loss) else repr(final_loss))
     out = {
         'metric': 'utterances/s LAS train step (B=64 per GPU, T=800, F=40)', 'value': round(utt_s, 2),
         'unit': 'utterances/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
         'ms_per_step': round(ms, 3), 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
         'dtype': 'bf16', 'data': 'synthetic', 'config': config,
-        'roofline': {'bound': 'mfma', 'kernel': dom['name'],
-                     'achieved': dom['tflops'], 'peak': PEAK_BF16_TFLOPS, 'unit': 'TFLOP/s',
-                     'frac': dom['frac'], 'traffic': traffic, 'traffic_source': traffic_src,
-                     'traffic_stale': traffic_stale, 'csrc_digest': csrc_digest(),
-                     'kernel_ms_per_step': dom['ms_per_step'], 'launches_per_step': dom['launches_per_step'],
-                     'algorithmic_flops_per_step': dom['algorithmic_flops'],
-                     'kernels': kernels,
-                     'whole_step_lstm_gemm_tflops_per_gpu': round(step_tflops, 3),
-                     'whole_step_frac': round(step_tflops / PEAK_BF16_TFLOPS, 6)},
     }
+    if args.full:
+        f_in, f_rec = lstm_gemm_flops_per_utt(c)
+        dom = kernels[0]         # the dominant kernel = the family with the largest time per step
+        # the committed PMC passes are of the default configuration's step: another configuration's kernels (other unit
+        # counts, other shapes) have no counter evidence and say so
+        traffic, traffic_src, traffic_stale = pmc_traffic(dom['family']) if args.config == 'metric-M' else (None, None, None)
+        step_tflops = 3 * (f_in + f_rec) * utt_s / world / 1e12
+        out['roofline'] = {'bound': 'mfma', 'kernel': dom['name'],
+                           'achieved': dom['tflops'], 'peak': PEAK_BF16_TFLOPS, 'unit': 'TFLOP/s',
+                           'frac': dom['frac'], 'traffic': traffic, 'traffic_source': traffic_src,
+                           'traffic_stale': traffic_stale, 'csrc_digest': csrc_digest(),
+                           'kernel_ms_per_step': dom['ms_per_step'], 'launches_per_step': dom['launches_per_step'],
+                           'algorithmic_flops_per_step': dom['algorithmic_flops'],
+                           'kernels': kernels,
+                           'whole_step_lstm_gemm_tflops_per_gpu': round(step_tflops, 3),
+                           'whole_step_frac': round(step_tflops / PEAK_BF16_TFLOPS, 6)}
     if errors:
         out['error'] = '; '.join(errors)
-    if world == 1 and not args.no_cpu_baseline and c.get('dec_layers', 1) == 1 and c.get('pyramidal', True):
+    if args.full and world == 1 and not args.no_cpu_baseline and c.get('dec_layers', 1) == 1 and c.get('pyramidal', True):
         out['cpu_baseline'] = cpu_baseline(c, args.cpu_sample)       # (the stand-ins are built for the headline architecture family)
     return out, rc
 

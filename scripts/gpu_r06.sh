@@ -86,9 +86,9 @@ case $R in
         LAS_HIP_LIB=$PWD/phones-las_amd/liblas_hip_stamps.so python scripts/gpu_dec_stamps.py > gpurun_out/r06_dec_stamps_metricM.txt 2>&1
       fi
       bash scripts/gpu_pmc.sh r06 > gpurun_out/r06_pmc.out 2>&1
-      timeout 1200 python bench.py --steps 30 --warmup 5 2>&1 | tail -1 > gpurun_out/r06_bench_metricM.json
+      timeout 1200 python bench.py --full --steps 30 --warmup 5 2>&1 | tail -1 > ${LOG%/*}/r06_bench_metricM.json
       for c in metric-M-ragged metric-M-stochastic metric-L cfg4 cfg5 cfg1 default-arch two-cell-bottom-only; do
-        timeout 400 python bench.py --config $c --steps 20 --warmup 3 --no-cpu-baseline 2>&1 | tail -1 > gpurun_out/r06_bench_$c.json
+        timeout 400 python bench.py --full --config $c --steps 20 --warmup 3 --no-cpu-baseline 2>&1 | tail -1 > ${LOG%/*}/r06_bench_$c.json
       done
       python - <<PY
 import json

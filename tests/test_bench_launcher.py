@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -60,7 +62,7 @@ def test_bare_multi_gpu_invocation_becomes_the_launcher(tmp_path):
 
 
 def _epilogue_worker(rank, world, port, ret):
-    """bench.epilogue on CPU under gloo: the per-kernel timing pass re-runs a step that contains the gradient all-reduce, so
+    """bench.epilogue (--full) on CPU under gloo: the per-kernel timing pass re-runs a step that contains the gradient all-reduce, so
     EVERY rank has to run it (rank 0 alone used to wait there for peers that had already left -- this worker
     would hang and the test time out).  One rank reports a non-finite loss: every rank must leave with exit code 1 and
     rank 0's record must carry the `error` field next to the measured value."""
@@ -88,7 +90,7 @@ def _epilogue_worker(rank, world, port, ret):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return bool(t.item() > 0)
 
-    args = argparse.Namespace(steps=10, warmup=2, no_cpu_baseline=True, cpu_sample=16, config='metric-M')
+    args = argparse.Namespace(steps=10, warmup=2, full=True, no_cpu_baseline=True, cpu_sample=16, config='metric-M')
     loss = float('nan') if rank == 1 else 1.25
     out, rc = bench.epilogue(rank, world, 0.0626, loss, [], eager_step, bench.CONFIGS['metric-M'], args,
                              {'workload': 'metric-M'}, any_rank, dist.barrier, table_fn=table_fn)
@@ -111,6 +113,51 @@ def test_epilogue_runs_the_timing_pass_on_every_rank_and_reports_errors_in_the_j
     assert 'not finite' in out0['error'] and out0['value'] == round(64 * 2 * 10 / 0.0626, 2)
     assert out0['n_gpus'] == 2 and out0['roofline']['kernel'].startswith('lstm_bwd') and 'traffic_stale' in out0['roofline']
     json.dumps(out0)                                           # the record serialises (NaN loss is kept as a string)
+
+
+def test_plain_epilogue_reports_the_timed_steps_only(monkeypatch):
+    """Without --full the epilogue runs no step of its own: no per-kernel timing pass, no roofline, no CPU baseline.  The
+    headline fields, and the error report of an invalid run, stay."""
+    bench = _bench()
+    monkeypatch.setattr(bench, 'cpu_baseline', lambda *a, **k: pytest.fail('cpu_baseline in a plain run'))
+    args = bench.arg_parser().parse_args(['--gpus', '1', '--steps', '10', '--warmup', '2'])
+    assert not args.full and args.dump_outputs is None
+    calls = []
+    run = lambda loss, status: bench.epilogue(0, 1, 0.0626, loss, status, lambda: calls.append('step'), bench.CONFIGS['metric-M'],
+                                              args, {'workload': 'metric-M'}, lambda f: bool(f), lambda: calls.append('barrier'),
+                                              table_fn=lambda step, c: calls.append('table') or [])
+    out, rc = run(1.25, [])
+    assert rc == 0 and calls == []
+    assert 'roofline' not in out and 'cpu_baseline' not in out and 'error' not in out
+    assert out['value'] == round(64 * 10 / 0.0626, 2) and out['ms_per_step'] == round(62.6 / 10, 3) and out['steps'] == 10
+    assert out['unit'] == 'utterances/s' and out['higher_is_better'] is True and out['dtype'] == 'bf16' and out['metric']
+    out, rc = run(float('nan'), [7])
+    assert rc == 1 and 'bounded-wait timeout' in out['error'] and 'not finite' in out['error'] and calls == []
+    json.dumps(out)
+
+
+def test_dump_outputs_stays_within_its_budget_and_samples_the_same_elements_every_time(tmp_path):
+    import numpy as np
+    import torch
+    bench = _bench()
+    assert bench.DUMP_BYTES == 64 * 10 ** 6
+    logits = torch.randn(4, 5, 6).to(torch.bfloat16)
+    outs = {'loss': torch.tensor([1.5]), 'logits': logits, 'params': torch.arange(300000, dtype=torch.float32),
+            'acc': np.arange(3, dtype=np.float64)}
+    budget = 600000                                  # bytes: the parameters do not fit in full
+    w1 = bench.dump_outputs(outs, str(tmp_path / 'a'), budget=budget)
+    w2 = bench.dump_outputs(outs, str(tmp_path / 'b'), budget=budget)
+    assert w1 == w2 and sorted(w1) == ['acc', 'logits', 'loss', 'params']
+    assert sum(os.path.getsize(str(tmp_path / 'a' / f)) for f in os.listdir(str(tmp_path / 'a'))) <= budget
+    load = lambda d, n: np.load(str(tmp_path / d / (n + '.npy')))
+    assert load('a', 'loss').dtype == np.float32 and load('a', 'loss').tolist() == [1.5]
+    assert load('a', 'acc').dtype == np.float64 and load('a', 'acc').tolist() == [0.0, 1.0, 2.0]
+    assert load('a', 'logits').dtype == np.float32 and np.array_equal(load('a', 'logits'), logits.float().numpy())
+    p = load('a', 'params')
+    assert p.dtype == np.float32 and w1['params'] == [p.size, 300000] and 100000 < p.size < 300000
+    assert np.all(np.diff(p) > 0) and np.array_equal(p, load('b', 'params'))     # a fixed sample, in index order
+    full = bench.dump_outputs(outs, str(tmp_path / 'c'))                         # the default budget: everything in full
+    assert full['params'] == [300000, 300000] and np.array_equal(load('c', 'params'), np.arange(300000, dtype=np.float32))
 
 
 def _probe_worker(rank, world, port, ret):
