@@ -872,6 +872,19 @@ int las_fe_batch_delta(const float* x, int64_t ldx, const int32_t* frame_off, in
                        const float* taps1, const float* lo1, const float* hi1, const float* taps2, const float* lo2,
                        const float* hi2, int width, float* out, int64_t ldo, void* stream);
 
+/* Resampling in front of the front-end (librosa 0.7.1 load -> resample(res_type='kaiser_best') = resampy 0.2.2 resample_f,
+ * then fix_length) over a ragged batch in one launch; no workspace.  `x` holds the mono float32 signals back to back,
+ * in_off[n_utt + 1] / out_off[n_utt + 1] (device int64) their first input / output samples.  Per utterance (device arrays):
+ * n_valid[u] = int(len * ratio) outputs are interpolated, the rest up to out_off[u + 1] (ceil(len * ratio)) are zeros;
+ * ratio[u] = target_sr / orig_sr as a double, 1.0 copying the signal unchanged; the time register as segments
+ * seg_off[n_utt + 1] (int32) into seg_t (int64) / seg_tr / seg_step (double): tr_t = seg_tr[b] + (t - seg_t[b]) * seg_step[b]
+ * for the last b with seg_t[b] <= t (audio.time_segments).  `half`: the UNSCALED float64 half window, nwin + 1 entries (the
+ * last repeated); win = half * ratio (ratio < 1) and its differences are formed on the fly.  Every operation is the separately
+ * rounded float64 operation resampy performs, in its order: results are bit-identical to that arithmetic. */
+int las_resample_batch(const float* x, const int64_t* in_off, const int64_t* out_off, const int64_t* n_valid, const double* ratio,
+                       const int32_t* seg_off, const int64_t* seg_t, const double* seg_tr, const double* seg_step,
+                       const double* half, int nwin, int n_utt, int64_t total_out, float* y, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Input path (utils/dataset_utils.py:138-283 of the reference: tf.data.TFRecordDataset ->
  * tf.parse_single_sequence_example -> (x - mean) / std -> padded_batch).  Host functions; `data` is the image of a

@@ -8,8 +8,8 @@ The signal-processing tables (periodic Hann window, DFT twiddles, Slaney / HTK m
 Savitzky-Golay taps) are built here in float64 and handed to the table-driven kernels of csrc/frontend.hip.
 The speechpy backend (round 6) runs on the same kernels with speechpy==2.4's tables -- rectangular frames without centering,
 its filterbank, its feature-axis differences -- restated from the published source of that release (requirements.txt:19; the
-package is not under /root/reference): see oracle/frontend_oracle.py for the quirks that are kept.  The lyon cochlear model and
-audio decoding are out of scope (SURVEY.md §2a #9)."""
+package is not under /root/reference): see oracle/frontend_oracle.py for the quirks that are kept.  The lyon cochlear model is out of
+scope (SURVEY.md §2a #9); audio decoding and resampling to 16 kHz are phones-las_amd/audio.py."""
 import functools
 
 import numpy as np

@@ -7,13 +7,15 @@ statistics = MEAN of the per-utterance mean / std (quirk B5), vocabulary = most 
 --backend speechpy (round 6) runs speechpy==2.4's mfe / mfcc / extract_derivative_feature on the same kernels
 (phones-las_amd/frontend.py; utterance by utterance, as the reference's forced n_jobs = 1, preprocess_all.py:228-230).
 
-Not on this path: audio decoding other than 16 kHz PCM WAV (the reference calls librosa.load),
-lyon features, espeak-ng text->IPA: texts whose language column is not 'arpabet'/'ipa' are refused for --targets phones /
-binary_features."""
+Audio: librosa.load(path, sr=16000, mono=True) of the reference (preprocess_all.py:61) is phones-las_amd/audio.py: RIFF WAV /
+NIST SPHERE decoded on the host at any rate, channels averaged, and every --gpu_batch group resampled to 16 kHz in one launch
+(resampy 0.2.2 kaiser_best, bit for bit its arithmetic) before the batched front-end; 16-kHz files are not resampled.
+
+Not on this path: compressed audio (mp3 / flac / ogg), lyon features, espeak-ng text->IPA: texts whose
+language column is not 'arpabet'/'ipa' are refused for --targets phones / binary_features."""
 import argparse
 import os
 import sys
-import wave
 from collections import Counter
 
 import numpy as np
@@ -50,22 +52,43 @@ def parse_args(argv=None):
     return p.parse_args(argv)
 
 
-def read_wav(path):
-    with wave.open(path, 'rb') as w:
-        if w.getframerate() != SAMPLE_RATE or w.getsampwidth() != 2:
-            raise ValueError('%s: only 16 kHz 16-bit PCM WAV is decoded here (resample first)' % path)
-        data = np.frombuffer(w.readframes(w.getnframes()), dtype='<i2').astype(np.float32) / 32768.0
-        if w.getnchannels() > 1:
-            data = data.reshape(-1, w.getnchannels()).mean(1)
-    return data
+def read_audio(path):
+    """librosa.load(path, sr=None, mono=True): the decoded mono float32 signal and its native rate (phones-las_amd/audio.py)."""
+    from phones_las_amd import audio
+    y, sr = audio.read(path)
+    return audio.to_mono(y), sr
 
 
 def read_audio_and_text(path, text):
-    """preprocess_all.py:53-66."""
+    """preprocess_all.py:53-66; the signal at its native rate (resampled with the rest of its --gpu_batch group)."""
     text = ' '.join(text.split())
     for ch in ',.:;?!-_':
         text = text.replace(ch, '')
-    return read_wav(path), text.lower().split()
+    waveform, sr = read_audio(path)
+    return waveform, sr, text.lower().split()
+
+
+def to_sample_rate(waves, srs):
+    """librosa.load's resampling to 16 kHz of a group of signals: the ones at other rates in one resample_batch launch; if that
+    fails, signal by signal, a failure giving None (the reference's per-line try / except skips that line).  A group that is
+    all 16 kHz is returned as it is (the host arrays, as before any-rate decoding)."""
+    import torch
+    from phones_las_amd import audio
+    todo = [i for i, sr in enumerate(srs) if sr != SAMPLE_RATE]
+    if not todo:
+        return list(waves)
+    out = [torch.from_numpy(np.ascontiguousarray(w)).cuda() for w in waves]   # one device batch for the front-end
+    try:
+        for i, y in zip(todo, audio.resample_batch([waves[i] for i in todo], [srs[i] for i in todo], SAMPLE_RATE)):
+            out[i] = y
+    except Exception:  # noqa: BLE001
+        for i in todo:
+            try:
+                out[i] = audio.resample(waves[i], srs[i], SAMPLE_RATE)
+            except Exception as e:  # noqa: BLE001
+                print('Hopefully recoverable error: %s' % e)
+                out[i] = None
+    return out
 
 
 def main(args):
@@ -87,11 +110,16 @@ def main(args):
     def features_of(waves):
         """Features of a group of utterances: one batched pass; if that fails (one signal too short for the deltas, say) each
         utterance on its own, so that only the offending line is skipped, as the reference's per-line try / except does."""
+        ok = [w is not None for w in waves]
         try:
-            return [f.cpu().numpy() for f in frontend.calculate_acoustic_features_batch(args, waves)]
+            feats = iter(frontend.calculate_acoustic_features_batch(args, [w for w in waves if w is not None]))
+            return [next(feats).cpu().numpy() if k else None for k in ok]
         except Exception:  # noqa: BLE001
             out = []
             for w in waves:
+                if w is None:
+                    out.append(None)
+                    continue
                 try:
                     out.append(frontend.calculate_acoustic_features(args, w).cpu().numpy())
                 except Exception as e:  # noqa: BLE001
@@ -100,13 +128,14 @@ def main(args):
             return out
 
     with tfrecord.TFRecordWriter(args.output_file) as writer:
-        pending = []                     # (waveform, tokens) of the lines read so far: flushed every --gpu_batch utterances
+        pending = []                     # (waveform, native rate, tokens) of the lines read so far: flushed every --gpu_batch utterances
 
         def flush():
             nonlocal means, stds, total
             if not pending:
                 return
-            for (_, tokens), feats in zip(pending, features_of([w for w, _ in pending])):
+            waves = to_sample_rate([w for w, _, _ in pending], [sr for _, sr, _ in pending])
+            for (_, _, tokens), feats in zip(pending, features_of(waves)):
                 if feats is None:
                     continue
                 if args.save_norm:
@@ -119,7 +148,7 @@ def main(args):
         for line in lines:
             try:
                 filename, language, text = line.split(args.delimiter)
-                waveform, tokens = read_audio_and_text(filename, text.strip())
+                waveform, sr, tokens = read_audio_and_text(filename, text.strip())
             except Exception as e:  # noqa: BLE001  (the reference skips unreadable lines, preprocess_all.py:177-181)
                 print('Failed to read audio or text! Exception: %s' % e)
                 continue
@@ -137,7 +166,7 @@ def main(args):
             # (the vocabulary counts a line's tokens BEFORE its features are formed, as the reference does,
             # preprocess_all.py:147-148: a line whose audio then fails still contributes to vocab.txt -- ADVICE r3)
             vocabulary.update(tokens)
-            pending.append((waveform, tokens))
+            pending.append((waveform, sr, tokens))
             if len(pending) >= max(1, args.gpu_batch):
                 flush()
         flush()
