@@ -885,6 +885,35 @@ int las_resample_batch(const float* x, const int64_t* in_off, const int64_t* out
                        const int32_t* seg_off, const int64_t* seg_t, const double* seg_tr, const double* seg_step,
                        const double* half, int nwin, int n_utt, int64_t total_out, float* y, void* stream);
 
+/* Frame-level binary-feature accuracy (infer.py --calc_frame_binf_accuracy; phones-las_amd/frame_binf.py), since version 104.
+ * las_attention_dtw_batch: per utterance u of a ragged batch of fp32 attention matrices, read in place (element offset att_off[u],
+ * rows[u] = U phones, cols[u] = T' frames, row stride ld[u] >= T'), in one launch: fastdtw 0.3.x
+ * dtw(range(U), range(T'), dist = -A) bit for bit (float64 table, ties up < left < diagonal), the reference's
+ * soft2hard_attention cleanup and attention_to_segments.  Outputs at int64 column offsets out_off[u] (T' entries each):
+ * run_lo / run_hi = the cleaned path's rows of each column, ph_st / ph_en = the phone range [st, en) of each frame's segment;
+ * n_seg[u] = the segment count (U = 0 or T' = 0: 0, empty runs lo 0 / hi -1, ranges [0, 0); -1: a shape outside
+ * u_max / t_max / ld; -2: the path left the grid, which only a NaN table makes).  u_max / t_max bound the batch's shapes
+ * (t_max <= 8191); a workspace of las_attention_dtw_workspace_bytes(u_max, t_max, n_utt) bytes holds the backpointers that do
+ * not fit in LDS (0 bytes: none needed, workspace may be NULL). */
+size_t las_attention_dtw_workspace_bytes(int u_max, int t_max, int n_utt);
+int las_attention_dtw_batch(const float* att, const int64_t* att_off, const int32_t* rows, const int32_t* cols, const int32_t* ld,
+                            int n_utt, int u_max, int t_max, const int64_t* out_off, int32_t* run_lo, int32_t* run_hi,
+                            int32_t* ph_st, int32_t* ph_en, int32_t* n_seg, void* workspace, size_t workspace_bytes, void* stream);
+/* las_frame_binf_count: per utterance u, per feature f < F (F <= 256), counts[u * F + f] = the number of frames j < n_frames[u]
+ * whose predicted and target values of feature f agree.  P: per-utterance uint8 matrices P_u [p_rows[u], F] at element offsets
+ * p_off[u] (nonzero = 1).  Markup segments seg_off[u] .. seg_off[u + 1] - 1 (int64 offsets into seg / seg_binf): seg[2k], seg[2k+1]
+ * = its frames [st, en) (st >= 0; en <= st is empty), seg_binf[k * F ..] its uint8 target row; the target of frame j = the OR of
+ * the rows of every segment covering it.  Prediction with att == NULL: the OR of the P_u rows [ph_st, ph_en) of frame j (int32
+ * arrays at offsets frame_off[u], las_attention_dtw_batch's outputs).  With att (--use_markup_segments; attention at att_off[u],
+ * att_cols[u] frames, row stride att_ld[u], at least min(5, p_rows[u]) rows): each markup segment takes the P_u row
+ * argmax_{r < min(5, U)} max_{f in [st, max(en, st + 1)) and f < att_cols} A[r, f] (first maximum; seg_phone[k] = that row, -1 when
+ * the window or U is empty: no row), and frame j's prediction is the OR of the rows its covering segments took. */
+int las_frame_binf_count(const uint8_t* P, const int64_t* p_off, const int32_t* p_rows, int F, const int32_t* ph_st,
+                         const int32_t* ph_en, const int64_t* frame_off, const int32_t* seg, const uint8_t* seg_binf,
+                         const int64_t* seg_off, const float* att, const int64_t* att_off, const int32_t* att_cols,
+                         const int32_t* att_ld, const int32_t* n_frames, int n_utt, int32_t* seg_phone, int32_t* counts,
+                         void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Input path (utils/dataset_utils.py:138-283 of the reference: tf.data.TFRecordDataset ->
  * tf.parse_single_sequence_example -> (x - mean) / std -> padded_batch).  Host functions; `data` is the image of a

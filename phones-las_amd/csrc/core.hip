@@ -34,10 +34,12 @@ extern "C" int las_set_knob(const char* name, int value) {
   return LAS_OK;
 }
 
+// 104: las_attention_dtw_batch / las_attention_dtw_workspace_bytes / las_frame_binf_count (csrc/align.hip, frame_binf.py) added,
+// nothing else changed;
 // 103: las_resample_batch (csrc/resample.hip: resampy 0.2.2 kaiser_best over a ragged batch, audio.py) added, nothing else changed;
 // 101 (round 6): host.cpp split off, the recurrent backward launches eight-wave workgroups at 64 / 128 / 256 units (same entry points,
 // same results); 100 (round 5) removed five entry points and gave las_lstm_fwd::reserved1 a meaning (rows_per_slice).
-extern "C" int las_version(void) { return 103; }
+extern "C" int las_version(void) { return 104; }
 
 namespace {
 
