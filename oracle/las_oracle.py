@@ -941,7 +941,8 @@ def edit_distance(hyp, truth, eos_id=EOS_ID, mapping=None):
 def model_loss(hp: HP, params, batch, mxu='f64', stochastic=None):
     """Forward of las_model_fn in TRAIN mode (model_helper.py:205-227,319-357).  batch keys:
     encoder_inputs [B,T,F], source_sequence_length, targets_inputs, targets_outputs,
-    target_sequence_length.  Returns (audio_loss, aux dict)."""
+    target_sequence_length.  stochastic: the realised draws (enc_masks, dec_masks, sample_select, sample_ids, sample_vecs,
+    att_noise); stochastic['decoders'][scope] overrides the decoder keys for one decoder.  Returns (audio_loss, aux dict)."""
     x = batch['encoder_inputs']
     st = stochastic or {}
     (mem, mem_len), state = listener(x, batch['source_sequence_length'], params, hp.encoder, mxu,
@@ -949,10 +950,11 @@ def model_loss(hp: HP, params, batch, mxu='f64', stochastic=None):
     gq = _g(make_q(mxu))
     loss, aux = None, {'memory': mem, 'memory_len': mem_len, 'state': state}
     for scope, kind in speller_plan(hp.decoder):                                 # model_helper.py:211-227,319-342
+        ds = {**st, **st.get('decoders', {}).get(scope, {})}    # a decoder's own draws (--multitask), else the shared ones
         logits, sp = speller_train(hp, params, mem, mem_len, state, batch['targets_inputs'],
-                                   batch['target_sequence_length'], mxu, sample_select=st.get('sample_select'),
-                                   sample_ids=st.get('sample_ids'), noise=st.get('att_noise'), in_masks=st.get('dec_masks'),
-                                   scope=scope, kind=kind, sample_vecs=st.get('sample_vecs'))
+                                   batch['target_sequence_length'], mxu, sample_select=ds.get('sample_select'),
+                                   sample_ids=ds.get('sample_ids'), noise=ds.get('att_noise'), in_masks=ds.get('dec_masks'),
+                                   scope=scope, kind=kind, sample_vecs=ds.get('sample_vecs'))
         if kind == 'sigmoid':
             logits = gq(logits)
             tb = torch.as_tensor(hp.decoder.binf_map, dtype=DT).t()[batch['targets_outputs']]

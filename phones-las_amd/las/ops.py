@@ -517,6 +517,10 @@ def bilstm_backward(rec, dy, d_state, grads, need_dx=True, overlap=None, defer_w
     exposed: no recurrence follows that would hide the weight-gradient products (the bottom layer): the two directions'
     products then run on two streams at once instead of one after the other."""
     B, T, H, D, Dp, nd = rec['B'], rec['T'], rec['H'], rec['D'], rec['Dp'], rec['nd']
+    if need_dx and rec.get('dropped') is not None and rec.get('keep', 1.0) < 1.0 and D != Dp:
+        # the forward drew the masks at r*Dp + c (las_dropout_bf16[_pair] over [B*T, Dp]); las_gemm_nt_masked and las_dropout_bwd
+        # regenerate them at r*D + c.  Only the bottom layer has D < Dp, and nothing needs its dX.
+        raise ValueError('bilstm_backward: dX through input dropout needs D == Dp (got D=%d, Dp=%d)' % (D, Dp))
     w = rec['weights']
     dev = dy.device
     dz = torch.empty(B, T, nd * 4 * H, dtype=torch.bfloat16, device=dev)

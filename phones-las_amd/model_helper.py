@@ -142,6 +142,22 @@ def speller_plan(d):
     return [('speller', kind)]
 
 
+def speller_seed(step_seed, k):
+    """Seed of decoder k's draws (input dropout, scheduled sampling, monotonic noise) in the step drawing with `step_seed`.
+    Every decoder uses the same stream numbers, so the decoders of a --multitask model would draw the same numbers -- sample
+    at the same (utterance, step) cells, drop the same inputs -- under one seed; the reference's helpers draw independently.
+    Decoder 0 keeps the step's seed (its recorded draws stay put); decoder k >= 1 gets lowbias32(step_seed ^ k * golden)."""
+    if k == 0:
+        return step_seed
+    x = (step_seed ^ (k * 0x9E3779B9)) & 0xFFFFFFFF
+    x ^= x >> 16
+    x = (x * 0x7feb352d) & 0xFFFFFFFF
+    x ^= x >> 15
+    x = (x * 0x846ca68b) & 0xFFFFFFFF
+    x ^= x >> 16
+    return x & 0x7fffffff
+
+
 def tf_variable_name_map(params):
     """{product variable name: name of the same tensor in the reference's TF-1 graph}, for a checkpoint importer.  Layouts are
     identical (kernel [D+H, 4H], gate order i, j, f, o, zero bias with the forget bias added in the cell); only names differ.
@@ -648,12 +664,12 @@ class LasModel:
         (mem, mem_len), state = self.listener.forward(x, src_len, TRAIN, seed=step_seed, after_first_layer=images_ready)
         U = num_steps if num_steps is not None else int(tlen.max().item())
         loss, logits, dlogits = None, None, []
-        for mod, kind in self.spellers:          # audio_loss = sum of the decoders' losses (model_helper.py:337-342)
+        for k, (mod, kind) in enumerate(self.spellers):     # audio_loss = sum of the decoders' losses (model_helper.py:337-342)
             extra = {'overlap': self.overlap} if isinstance(mod, las_model.Speller) else {}
             if extra and kind == 'phones':
                 # the fused speller forms the loss itself when it can (las_proj_ce: projection + loss + product back in one launch)
                 extra['loss_targets'] = (tout, tlen, 1.0 / self.world_size)
-            lg = mod.forward_train(mem, mem_len, state, tin, U, seed=step_seed, **extra)
+            lg = mod.forward_train(mem, mem_len, state, tin, U, seed=speller_seed(step_seed, k), **extra)
             if extra and getattr(mod, 'fused_loss', None) is not None:
                 l_, dl = mod.fused_loss
             elif kind == 'sigmoid':

@@ -346,3 +346,80 @@ def test_checkpoint_resume_reproduces_the_stochastic_stream(tmp_path):
     other = mh.LasModel(params, seed=100)           # ... and the seed does matter
     run(other, 0, 6)
     assert not torch.equal(other.vars.flat, straight.vars.flat)
+
+
+def test_multitask_decoders_draw_independently_replayed():
+    """--multitask with input dropout and scheduled sampling: the phone decoder and the sigmoid-output binary decoder must not
+    share their draws (the reference's two helpers sample independently).  Each projection is biased so that every sampled
+    draw differs from the teacher's input -- token 0 for the phone decoder, the all-ones feature vector for the binary one --
+    so the (utterance, step) cells each decoder sampled can be read off what it was fed.  Identical patterns over the 56 cells
+    would have probability ~2^-56 under independent draws.  Both decoders' realised draws are then replayed through the oracle."""
+    import tests.rng_restated as R
+    from oracle import las_oracle as O
+    from phones_las_amd import model_helper as mh
+    from tests.test_gpu_binary_decoders import _toy_binf
+    keep, p = 0.8, 0.5
+    B, T, F, H, V, U, nf = 8, 12, 13, 64, 11, 8, 8
+    binf = _toy_binf(nf, V)
+    ohp, params = make_hparams(binf=binf, sigmoid=True, multitask=True, att='luong', sampling=p)
+    params.encoder.set_hparam('dropout', 1 - keep)
+    params.decoder.set_hparam('dropout', 1 - keep)
+    op = O.init_params(ohp, bias_scale=0.1)
+    op['speller/projection_layer/bias'][0] += 20.0            # token 0: never a teacher input (targets are >= 3, <s> / </s>)
+    op['speller_binf/projection_layer/bias'] += 20.0           # sigmoid(20) rounds to 1: every drawn feature is 1
+    model = mh.LasModel(params, binf2phone=binf)
+    model.load_variables(op)
+    src_len, tgt_len = [12, 7, 10, 12, 9, 11, 8, 12], [8, 6, 7, 8, 5, 8, 4, 8]
+    batch = make_batch(B=B, T=T, U=U, src_len=src_len, tgt_len=tgt_len)
+    tin = batch['targets_inputs']
+    assert not bool((tin[:, 1:] == 0).any())
+    feats, labels = to_device(batch)
+    model.vars.grad.zero_()
+    loss, logits, dlogits = model.forward_train(feats, labels)
+    (sp0, _), (sp1, kind1) = model.spellers
+    assert kind1 == 'sigmoid'
+    fed = sp0.saved['fed'].cpu().long()
+    X0 = sp1.saved['X'][0].float().cpu()
+    seed, seed1 = sp0.saved['seed'], sp1.saved['seed']          # what each decoder's backward regenerates its draws from
+    model.backward(dlogits)
+    torch.cuda.synchronize()
+    # phone decoder: read off the fed tokens, and they are the restated decisions
+    sel0 = (fed[:, 1:U] == 0).t().numpy()                     # [U-1, B]
+    assert bool((fed[:, 1:U][~torch.from_numpy(sel0.T)] == tin[:, 1:U][~torch.from_numpy(sel0.T)]).all())
+    for t in range(U - 1):
+        assert np.array_equal(sel0[t], R.select(B, p, seed, t))
+    # binary decoder: the restated decisions under its own seed, checked against its operand rows (dropped in place at step t+1)
+    sel1 = np.stack([R.select(B, p, seed1, t) for t in range(U - 1)])
+    teacher = torch.as_tensor(binf, dtype=torch.float32).t()[tin]        # [B, U, nf]
+    for t in range(U - 1):
+        m = _mask(B * sp1.win[0], keep, seed1, sp1.in_stream(0, t + 1)).reshape(B, sp1.win[0])[:, :nf].float()
+        want = torch.where(torch.from_numpy(sel1[t])[:, None], torch.ones(B, nf), teacher[:, t + 1]) * m
+        assert torch.equal(X0[:, t + 1, :nf], want), t
+    assert sel0.any() and sel1.any() and not sel0.all() and not sel1.all()
+    assert not np.array_equal(sel0, sel1)                     # the two decoders sample at different cells
+    assert seed == model.last_seed and seed1 == mh.speller_seed(seed, 1) != seed
+    # replay: listener masks (shared), each decoder's own masks and draws
+    enc_masks = []
+    for l, (Tl, Dp, D) in enumerate([(12, 16, F), (12, 2 * H, 2 * H)]):
+        enc_masks.append(tuple(_mask(B * Tl * Dp, keep, seed, 16 + 2 * l + d).reshape(B, Tl, Dp)[..., :D] for d in range(2)))
+    fw = V + sp0.M
+    dm0 = _mask(U * B * fw, keep, seed, sp0.DEC_STREAM).reshape(U, B, fw)
+    E, T0 = sp1.E, sp1.T0
+    dm1 = []
+    for t in range(U):
+        m = _mask(B * sp1.win[0], keep, seed1, sp1.in_stream(0, t)).reshape(B, sp1.win[0])
+        dm1.append([torch.cat([m[:, :E], m[:, T0:]], 1)])
+    ids = [fed[:, t + 1] for t in range(U - 1)] + [torch.zeros(B, dtype=torch.long)]
+    last = torch.zeros(B, dtype=torch.bool)
+    st = {'enc_masks': enc_masks, 'decoders': {
+        'speller': {'dec_masks': [dm0[t] for t in range(U)], 'sample_ids': ids,
+                    'sample_select': [torch.from_numpy(sel0[t]) for t in range(U - 1)] + [last]},
+        'speller_binf': {'dec_masks': dm1, 'sample_vecs': torch.ones(U, B, nf, dtype=DT),
+                         'sample_select': [torch.from_numpy(sel1[t]) for t in range(U - 1)] + [last]}}}
+    out = O.train_step(ohp, op, None, None, 1, batch, mxu='bf16', stochastic=st)
+    for b, n in enumerate(tgt_len):
+        assert relerr(logits[b, :n, :V], out['aux']['logits'][b, :n]) < 2e-2
+    assert abs(float(loss) - float(out['audio_loss'])) < 2e-2 * abs(float(out['audio_loss']))
+    for name, _, _ in model.vars.table:
+        g = out['grads'][name] - ohp.l2_reg_scale * op[name]
+        assert relerr(model.vars.grads[name], g) < 2e-2, name
