@@ -26,6 +26,7 @@ __device__ __forceinline__ void lds_barrier() {
 }
 
 constexpr int NT = 512;               // threads per workgroup (one workgroup per utterance)
+constexpr size_t CTC_LDS_BYTES = 160 * 1024 - 64;     // dynamic LDS of a launch (the CU's 160 KiB less the kernel's static part)
 __global__ __launch_bounds__(NT) void ctc_kernel(const float* __restrict__ logits, int64_t ldl, const int32_t* __restrict__ labels,
                                                   int64_t ldlab, const int32_t* __restrict__ label_len,
                                                   const int32_t* __restrict__ logit_len, int T, int C, int U, int blank,
@@ -287,12 +288,20 @@ extern "C" int las_ctc_loss(const float* logits, int64_t ldl, const int32_t* lab
   const int Sp = 2 * U + 1 + 3;
   const size_t lds0 = (size_t)(2 * Sp) * sizeof(float) + (size_t)Sp * sizeof(int);
   LAS_REQUIRE(lds0 <= 64 * 1024, "las_ctc_loss: label length %d too long", U);
-  // + the gradient's staging area: as many frames of alpha + beta as 96 KiB hold (cfg4: all 100)
-  const int g_rows = (int)((96 * 1024) / ((size_t)Sp * sizeof(float))) < T ? (int)((96 * 1024) / ((size_t)Sp * sizeof(float))) : T;
-  const size_t lds = lds0 + (size_t)g_rows * Sp * sizeof(float) + (size_t)(2 * C + 2) * sizeof(int) + (size_t)(2 * Sp) * sizeof(float);
+  // what the kernel needs whatever the staging area: the columns and the states (lds0), the class counters, beta's columns
+  const size_t fixed = lds0 + (2 * (size_t)C + 2) * sizeof(int) + (size_t)(2 * Sp) * sizeof(float);
+  LAS_REQUIRE(fixed <= CTC_LDS_BYTES, "las_ctc_loss: C=%d classes with U=%d labels need %zu bytes of LDS, the limit is %zu", C, U,
+              fixed, CTC_LDS_BYTES);
+  // + the gradient's staging area: as many frames of alpha + beta as 96 KiB hold (cfg4: all 100), or as what is left of the budget
+  // holds; none (g_rows = 0) is the kernel's walk through global memory
+  const size_t row_bytes = (size_t)Sp * sizeof(float);
+  size_t rows = (96 * 1024) / row_bytes;
+  if ((CTC_LDS_BYTES - fixed) / row_bytes < rows) rows = (CTC_LDS_BYTES - fixed) / row_bytes;
+  const int g_rows = rows < (size_t)T ? (int)rows : T;
+  const size_t lds = fixed + (size_t)g_rows * row_bytes;
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ctc_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ctc_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)CTC_LDS_BYTES);
     attr_set = true;
   }
   float* lp_ws = reinterpret_cast<float*>(workspace);

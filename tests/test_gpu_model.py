@@ -311,7 +311,10 @@ def test_weight_noise_hits_kernels_only():
 def test_ctc_kernel_matches_torch_ctc_loss(T, C, Cp, U):
     """(round 6: the kernel's data movement was rewritten -- a row per wave with one or two classes per lane, or the loop form beyond
     128 classes; one state per thread with the two recursions side by side, or the strided form beyond 256 states; state lists per
-    class, the long ones a frame per lane -- : the cases cover each form; profiles/r06_ctc_ab.txt has the bit-identity with round 5.)"""
+    class, the long ones a frame per lane.  The cases here have C = 9, 30 and 150 and S up to 281: one class per lane and the loop
+    form, both recursions; the two-classes-per-lane form (64 < C <= 128), the switch at S = 255 / 257, long lists of a class other
+    than the blank and the ragged edges are in tests/test_gpu_loss_heads.py, against float64.  profiles/r06_ctc_ab.txt has the
+    bit-identity with round 5.)"""
     from phones_las_amd import hip
     import torch.nn.functional as F
     torch.manual_seed(0)
