@@ -61,8 +61,8 @@ enum las_att_norm {      /* how scores become alignments (SURVEY.md Appendix A.6
 
 int las_version(void);
 const char* las_last_error(void);
-/* The library's diagnostics / A-B switches are integer environment variables (LAS_*: slice heights, member counts, kernel
- * families; see README) that it reads ONCE, at their first use.  las_set_knob overrides one afterwards (the tests' hook). */
+/* The library's switches are integer environment variables (LAS_LSTM_ROWS, the slice height, is the one left; see README) that
+ * it reads ONCE, at their first use.  las_set_knob overrides one afterwards (the tests' hook). */
 int las_set_knob(const char* name, int value);
 
 /* ------------------------------------------------------------------------------------------

@@ -4278,8 +4278,7 @@ extern "C" int las_decoder_persist_fwd(const las_dec_persist* p, void* stream) {
     LAS_LAUNCH_CHECK("persistent decoder fwd (attention layer / monotonic) launch");
     return LAS_OK;
   }
-  const int lean_mode = las_knob("LAS_DEC_LEAN", 1);     // 0: the general body also where the written-out one applies (diagnostics)
-  if (lean_mode && (p->sampling_prob <= 0.f || s->Hd <= 256) && s->tok_rows &&
+  if ((p->sampling_prob <= 0.f || s->Hd <= 256) && s->tok_rows &&
       persist_fwd_lean_ok(s->Hd, s->M, s->Tm, p->U, s->attention, s->norm) && p->K_in / 32 <= (s->Hd == 512 ? 80 : 48)) {
     const size_t lbytes = lean_layout(s->Hd, s->Tm, s->M, p->U).total_bytes;
 #define LAS_LEAN_LAUNCH(...)                                                                                                    \
@@ -4502,10 +4501,9 @@ extern "C" int las_decoder_seq_bwd(const las_dec_seq_bwd* p, void* stream) {
     attr = true;
   }
   // Bahdanau scores: d(keys) in registers when the utterance's frames fit SEQ_NPK passes of the 256 / (Hd / 8) frame phases
-  // (Tm <= 200 at 256 units, 400 at 128); LAS_DEC_SEQ_REGK=0 keeps the read-modify-write in memory (A/B measurements)
-  const bool regk_on = las_knob("LAS_DEC_SEQ_REGK", 1) != 0;
+  // (Tm <= 200 at 256 units, 400 at 128); longer ones keep the read-modify-write in memory
   const int P = 256 / (s->Hd / 8);
-  const bool regk = additive && regk_on && q.A > 0 && q.vw && (s->Tm + P - 1) / P <= SEQ_NPK;
+  const bool regk = additive && q.A > 0 && q.vw && (s->Tm + P - 1) / P <= SEQ_NPK;
   // ... and four workgroups per utterance (the caller hands in the exchange workspace) when every one of them finds a CU of its
   // own -- they wait for one another -- and a quarter of the frames fits SEQ_NPK4 passes
   static const int cus = [] { int dev = 0, n = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n; }();

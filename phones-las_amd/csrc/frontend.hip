@@ -434,21 +434,16 @@ extern "C" int las_fe_batch_melspec(const float* waves, const int64_t* wave_off,
     hipLaunchKernelGGL(fill_f32_kernel, dim3((n_utt + 255) / 256), dim3(256), 0, st, utt_max, n_utt, -INFINITY);
     LAS_LAUNCH_CHECK("fe batch max init");
   }
-  const int blocked = las_knob("LAS_FE_BLOCKED", 1);          // 0: one frame per workgroup again (diagnostics, A/B timing)
-  const int fb16 = las_knob("LAS_FE_FB", 8) == 16 ? 1 : 0;     // 16: sixteen frames per workgroup (A/B)
+  // eight frames per workgroup; one frame per workgroup where eight do not fit the LDS (large n_fft) or there are too few frames
   constexpr int FB = 8;
-  if (blocked && fb16 && (size_t)16 * (n_fft + bins) * sizeof(float) <= 60 * 1024 && total_frames >= 64)
-    hipLaunchKernelGGL(batch_melspec_blocked_kernel<16>, dim3((total_frames + 15) / 16), dim3(256),
-                       (size_t)16 * (n_fft + bins) * sizeof(float), st, waves, wave_off, frame_off, n_utt, total_frames, n_fft, hop,
-                       center ? n_fft / 2 : 0, power, window, costab, sintab, bins, mel, n_mels, epilogue, eps, scale, out, utt_max);
-  else if (blocked && (size_t)FB * (n_fft + bins) * sizeof(float) <= 60 * 1024 && total_frames >= 4 * FB)
+  if ((size_t)FB * (n_fft + bins) * sizeof(float) <= 60 * 1024 && total_frames >= 4 * FB)
     hipLaunchKernelGGL(batch_melspec_blocked_kernel<FB>, dim3((total_frames + FB - 1) / FB), dim3(256),
                        (size_t)FB * (n_fft + bins) * sizeof(float), st, waves, wave_off, frame_off, n_utt, total_frames, n_fft, hop,
                        center ? n_fft / 2 : 0, power, window, costab, sintab, bins, mel, n_mels, epilogue, eps, scale, out, utt_max);
   else
-  hipLaunchKernelGGL(batch_melspec_kernel, dim3(total_frames), dim3(256), (size_t)(n_fft + bins) * sizeof(float), st, waves, wave_off,
-                     frame_off, n_utt, n_fft, hop, center ? n_fft / 2 : 0, power, window, costab, sintab, bins, mel, n_mels, epilogue,
-                     eps, scale, out, utt_max);
+    hipLaunchKernelGGL(batch_melspec_kernel, dim3(total_frames), dim3(256), (size_t)(n_fft + bins) * sizeof(float), st, waves, wave_off,
+                       frame_off, n_utt, n_fft, hop, center ? n_fft / 2 : 0, power, window, costab, sintab, bins, mel, n_mels, epilogue,
+                       eps, scale, out, utt_max);
   LAS_LAUNCH_CHECK("fe batch melspec launch");
   return LAS_OK;
 }

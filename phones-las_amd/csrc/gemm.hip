@@ -1220,23 +1220,16 @@ static int gemm_nt(const las_bf16* A, int64_t lda, const las_bf16* B, int64_t ld
   }
   if (M <= 64 || N <= 64) return launch<64, 64, false>(g, batch, st);
   {
-    // The bulk products run on the LDS-DMA ring kernel.  Measured on the metric-M shapes (scripts/gpu_nt_ab.py, us):
+    // The bulk products run on the LDS-DMA ring kernel.  Measured on the metric-M shapes (round 2, us):
     //   K = 2048 (dX): 256 x 256 tiles, 32-deep x 4 stages (one workgroup per CU)      140 / 154  (register-staged: 188 / 203)
     //   K <= 1024 (x K_x with its fp32 output, keys): 256 x 128 tiles, 32-deep x 3 stages = 72 KiB, two workgroups
     //   per CU, so one's epilogue runs beside the other's K loop                          215 / 155 / 27  (251 / 199 / 30)
-    // LAS_GEMM_RING=0: register-staged kernels everywhere; 1: 256x128x64 (3 stages); 2: 256x256 wherever N allows; 4: the
-    // two-per-CU form everywhere (diagnostics, A/B timing)
-    const int ring = las_knob("LAS_GEMM_RING", 5);
-    if (ring && split_k == 1 && K % 64 == 0 && K >= 128 && M >= 1024 && N >= 128 && (ldc % 4 == 0 || out_bf16)) {
+    // The 256 x 256 ring runs the ping-pong schedule (round 5: the two waves of a SIMD alternate LOAD and MATH segments, +3-6 % on
+    // the K > 1024 shapes; on the two-per-CU 256 x 128 form it changed nothing -- two workgroups de-phase each other already).
+    if (split_k == 1 && K % 64 == 0 && K >= 128 && M >= 1024 && N >= 128 && (ldc % 4 == 0 || out_bf16)) {
       const bool wide = N >= 256 && N % 256 != 128;
-      if (ring == 1) return launch_ring<256, 128, 64, 3, 4>(g, batch, st);
-      if (ring == 4 || (ring >= 5 && !(wide && K > 1024))) return launch_ring<256, 128, 32, 3, 4>(g, batch, st);
-      // LAS_GEMM_PP (round 5): the ping-pong schedule of the 256 x 256 ring (the two waves of a SIMD alternate LOAD and MATH
-      // segments: +3-6 % on the K > 1024 shapes); 0: off.  (On the two-per-CU 256 x 128 form it changed nothing -- two workgroups
-      // de-phase each other already -- and that instantiation was removed in round 6.)
-      const int pp = las_knob("LAS_GEMM_PP", 1);
-      if (wide) return pp ? launch_ring<256, 256, 32, 4, 2, 8, true>(g, batch, st) : launch_ring<256, 256, 32, 4, 2>(g, batch, st);
-      return launch_ring<256, 128, 64, 3, 4>(g, batch, st);
+      if (wide && K > 1024) return launch_ring<256, 256, 32, 4, 2, 8, true>(g, batch, st);
+      return launch_ring<256, 128, 32, 3, 4>(g, batch, st);
     }
   }
   if (M >= 4096) return launch<128, 128, false, 32>(g, batch, st);      // the bulk products: three workgroups per CU
@@ -1477,14 +1470,12 @@ extern "C" int las_gemm_nt_bimg(const las_bf16* A, int64_t lda, const las_bf16* 
     hipDeviceProp_t prop;
     cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
   }
-  int ti = las_knob("LAS_BIMG_TI", 0);
-  if (ti < 6 || ti > 8) {
-    long best = -1;
-    for (int t = 8; t >= 6; --t) {
-      const long tiles = (long)((M + 32 * t - 1) / (32 * t)) * (N / 256);
-      const long cost = ((tiles + cus - 1) / cus) * t * (t == 8 ? 100 : t == 7 ? 105 : 112);
-      if (best < 0 || cost < best) { best = cost; ti = t; }
-    }
+  int ti = 8;
+  long best = -1;
+  for (int t = 8; t >= 6; --t) {
+    const long tiles = (long)((M + 32 * t - 1) / (32 * t)) * (N / 256);
+    const long cost = ((tiles + cus - 1) / cus) * t * (t == 8 ? 100 : t == 7 ? 105 : 112);
+    if (best < 0 || cost < best) { best = cost; ti = t; }
   }
   const dim3 grid(N / 256, (M + 32 * ti - 1) / (32 * ti), 1);
   auto go = [&](auto ti_tag) {
@@ -1549,9 +1540,8 @@ extern "C" int las_gemm_nt_stream_dirs(const las_bf16* A, int64_t lda, int64_t a
   }
   // persistent: two workgroups per CU would fit; whatever is resident on an XCD works through that XCD's queue, the rest of the
   // grid finds the queues empty and leaves
-  // LAS_STREAM_GRID: the producer's workgroups.  Measured in one call (metric-M): 96: 6.09 ms, 128: 6.02, 192: 6.02, 256: 6.04, 512: 6.05
-  int sgrid = las_knob("LAS_STREAM_GRID", 192);
-  if (sgrid < 8 || sgrid > 1024) sgrid = 192;
+  // The producer's workgroups.  Measured in one call (metric-M): 96: 6.09 ms, 128: 6.02, 192: 6.02, 256: 6.04, 512: 6.05
+  constexpr int sgrid = 192;
   hipLaunchKernelGGL((gemm_nt_ring_kernel<BM, BN, BK, STAGES, WGM, true>), dim3(sgrid), dim3(512), lds, (hipStream_t)stream, g);
   LAS_LAUNCH_CHECK("streamed gemm launch");
   return LAS_OK;
@@ -1643,11 +1633,9 @@ extern "C" int las_gemm_tn_lstm(const las_bf16* x, int64_t ldx, int D, const las
     g.partial = workspace;
     g.partial_stride = (int64_t)g.M * g.N;
   }
-  const int ring = las_knob("LAS_TN_RING", 1);          // 0: the register-staged 128 x 128 kernel (diagnostics, A/B timing)
-  if (ring && g.partial) {
-    // 128 x 512 output tiles (round 5; 128 x 64 per wave) where the caller asks for them and N is a multiple of 512;
-    // LAS_TN_WIDE=0 (A/B override): 128 x 256 everywhere
-    const bool wide = want_wide && las_knob("LAS_TN_WIDE", 1) != 0 && g.N % 512 == 0;
+  if (g.partial) {      // K split into a workspace: the ring kernels; unsplit: the register-staged 128 x 128 kernel
+    // 128 x 512 output tiles (round 5; 128 x 64 per wave) where the caller asks for them and N is a multiple of 512
+    const bool wide = want_wide && g.N % 512 == 0;
     static bool attr_ring = false;
     if (!attr_ring) {
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_ring_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize,

@@ -22,7 +22,7 @@ typedef __attribute__((ext_vector_type(4))) unsigned short u16x4;
 
 int las_check_hip(hipError_t e, const char* what);
 // Diagnostics / A-B knobs of the host code: integer environment variables READ ONCE, at their first use in the process (core.hip);
-// las_set_knob (the C-ABI's test hook) overrides a value afterwards -- the tests switch slice heights and member counts that way.
+// las_set_knob (the C-ABI's test hook) overrides a value afterwards -- the tests switch slice heights that way (LAS_LSTM_ROWS is the one knob left).
 int las_knob(const char* name, int default_value);
 
 #define LAS_LAUNCH_CHECK(what)                                   \

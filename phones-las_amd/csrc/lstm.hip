@@ -1410,9 +1410,6 @@ int slice_rows(int B, int H, int ndir, bool bwd) {
   return 16;
 }
 
-// LAS_LSTM_PREFETCH=0 launches the recurrent kernels without their prefetch companions (diagnostics)
-int prefetch_mode() { return las_knob("LAS_LSTM_PREFETCH", 1) != 0; }
-
 // 64-bit words of the workspace behind its header: what the last workgroup clears before the launch tags would wrap (the
 // whole exchange area of las_lstm_workspace_bytes, not only this launch's layout: forward and backward launches of every layer
 // share it)
@@ -1424,22 +1421,19 @@ int launch_fwd_as(float* xproj, const las_bf16* wp, const int32_t* length, las_b
   const CoopGeom g = geom(B, H, ndir, false, ROWS, G);
   unsigned* status = reinterpret_cast<unsigned*>(ws);
   u64* exch = reinterpret_cast<u64*>(reinterpret_cast<char*>(ws) + 64);
-  const int pf = prefetch_mode();
   // A streamed input product runs beside this launch (fi.ready): asking for LDS the kernel does not use keeps its workgroups
   // (72 KiB each) off the CUs of the chain's workgroups, as the backward launch does for the weight-gradient products.
   size_t hog = 0;
   if (fi.ready != nullptr) {
-    static int hog_kb = -1;
-    if (hog_kb < 0) {
-      constexpr int static_kb = (2 * 16 * (H + lds_pad(G)) * 2 + 1024 + 4096 + 1023) / 1024 + 2;
-      hog_kb = las_knob("LAS_STREAM_HOG_KB", 160 - static_kb - 6);     // (diagnostics: 0 lets the product's workgroups share the chain's CUs)
-      if (hog_kb > 160 - static_kb - 2) hog_kb = 160 - static_kb - 2;
-      if (hog_kb > 0) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_fwd_kernel<H, ROWS, G, KX>), hipFuncAttributeMaxDynamicSharedMemorySize, hog_kb * 1024);
-    }
-    hog = (size_t)(hog_kb > 0 ? hog_kb : 0) * 1024;
+    constexpr int static_kb = (2 * 16 * (H + lds_pad(G)) * 2 + 1024 + 4096 + 1023) / 1024 + 2;
+    constexpr int hog_kb = 160 - static_kb - 6;
+    static_assert(hog_kb > 0 && hog_kb <= 160 - static_kb - 2, "the request must fit beside the kernel's static LDS");
+    static const hipError_t asked = hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_fwd_kernel<H, ROWS, G, KX>), hipFuncAttributeMaxDynamicSharedMemorySize, hog_kb * 1024);
+    (void)asked;
+    hog = (size_t)hog_kb * 1024;
   }
-  hipLaunchKernelGGL((lstm_fwd_kernel<H, ROWS, G, KX>), dim3(pf ? g.blocks + g.companions : g.blocks), dim3(256), hog, st, xproj, wp, length, y,
-                     cbuf, c_last, h_last, exch, status, B, T, ndir, g.ngroups, pf, exch_words(B, H, ndir), fi);
+  hipLaunchKernelGGL((lstm_fwd_kernel<H, ROWS, G, KX>), dim3(g.blocks + g.companions), dim3(256), hog, st, xproj, wp, length, y,
+                     cbuf, c_last, h_last, exch, status, B, T, ndir, g.ngroups, /*pf=*/1, exch_words(B, H, ndir), fi);
   LAS_LAUNCH_CHECK("lstm fwd launch");
   return LAS_OK;
 }
@@ -1483,23 +1477,19 @@ int launch_bwd_as(const float* gates, const float* cbuf, const float* dy, const 
   const CoopGeom g = geom(B, H, ndir, true, ROWS, G);
   unsigned* status = reinterpret_cast<unsigned*>(ws);
   u64* exch = reinterpret_cast<u64*>(reinterpret_cast<char*>(ws) + 64);
-  const int pf = prefetch_mode();
   // The weight-gradient GEMMs of the layer above run beside this kernel on the second stream.  Asking for LDS the
   // kernel does not use keeps their workgroups (32 KiB of LDS each) off the CUs of the chain's workgroups: measured
   // 7.96 ms per metric-M step with them kept off, 8.5 ms when one fits beside a chain workgroup.  The request is what
   // the CU's 160 KiB leave after the kernel's own static LDS (dz tile 2 x 16 x (4*HS + 8) bf16, DMA scratch), minus a
   // margin smaller than any GEMM workgroup's need.
-  static int hog_kb = -1;
-  if (hog_kb < 0) {
-    constexpr int HS_ = H / G;
-    constexpr int coef_bytes = HW ? 2 * 2 * ((HS_ >= 64 ? HS_ / 64 : 1) * (ROWS / 4)) * 256 * 16 : 16;      // the helper waves' coefficient slots
-    constexpr int static_kb = (2 * 16 * (4 * HS_ + lds_pad(G)) * 2 + 1024 + coef_bytes + 1023) / 1024 + 1;
-    hog_kb = las_knob("LAS_LSTM_BWD_LDS_KB", 160 - static_kb - 6);
-    if (hog_kb > 160 - static_kb - 2) hog_kb = 160 - static_kb - 2;
-    if (hog_kb > 0)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_bwd_kernel<H, ROWS, G, PACK, HW>), hipFuncAttributeMaxDynamicSharedMemorySize, hog_kb * 1024);
-  }
-  hipLaunchKernelGGL((lstm_bwd_kernel<H, ROWS, G, PACK, HW>), dim3(pf ? g.blocks + g.companions : g.blocks), dim3(HW ? 512 : 256), (size_t)(hog_kb > 0 ? hog_kb : 0) * 1024, st,
+  constexpr int HS_ = H / G;
+  constexpr int coef_bytes = HW ? 2 * 2 * ((HS_ >= 64 ? HS_ / 64 : 1) * (ROWS / 4)) * 256 * 16 : 16;      // the helper waves' coefficient slots
+  constexpr int static_kb = (2 * 16 * (4 * HS_ + lds_pad(G)) * 2 + 1024 + coef_bytes + 1023) / 1024 + 1;
+  constexpr int hog_kb = 160 - static_kb - 6;
+  static_assert(hog_kb > 0 && hog_kb <= 160 - static_kb - 2, "the request must fit beside the kernel's static LDS");
+  static const hipError_t asked = hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_bwd_kernel<H, ROWS, G, PACK, HW>), hipFuncAttributeMaxDynamicSharedMemorySize, hog_kb * 1024);
+  (void)asked;
+  hipLaunchKernelGGL((lstm_bwd_kernel<H, ROWS, G, PACK, HW>), dim3(g.blocks + g.companions), dim3(HW ? 512 : 256), (size_t)hog_kb * 1024, st,
                      gates, cbuf, dy, dc_last, dh_last, kh, length, dz, exch, status, B, T, ndir, g.ngroups, exch_words(B, H, ndir));
   LAS_LAUNCH_CHECK("lstm bwd launch");
   return LAS_OK;
@@ -1514,24 +1504,17 @@ int launch_bwd(const float* gates, const float* cbuf, const float* dy, const flo
   // Eight-wave form (lstm_bwd_body, HW; round 6): helper waves own the HBM side of a step.  256 units 1.02 -> 0.88 us per step,
   // 128 units 1.05 -> 0.96 (profiles/r06_lstm_helper_waves_ab.txt, r06_hw128_ab.txt); not at 64 units (0.60 -> 0.66: a step is
   // too short for the eight-wave barrier), not at 512 / 1024 (a wave's 256 weight registers leave no room for a second wave on
-  // its SIMD), not on 16-row slices (four (row, unit) pairs per lane: registers).  LAS_LSTM_BWD_HW=0: the four-wave form (A/B).
-  const bool hw = (H == 256 || H == 128) && las_knob("LAS_LSTM_BWD_HW", 1) != 0;
+  // its SIMD), not on 16-row slices (four (row, unit) pairs per lane: registers).  Those keep the four-wave form.
   if constexpr (H == 256 || H == 512) {
     // exchanging chains without the row split.  On 8-row slices the partial sums travel as bf16 PAIRS (PACK, round 5: 512 units
     // 2.46 -> 2.06 us per step, metric-L 17.37 -> 16.67 ms; worst listener gradient against the oracle's bf16 / f64 model
     // 1.85e-3 -> 1.92e-3 / 1.166e-2 -> 1.173e-2 of max-abs; the fp32-granule form was removed in round 6).
-    if (rows == 4) {
-      if constexpr (H == 256) { if (hw) LAS_BWD(4, false, true); }
-      LAS_BWD(4, false, false);
-    }
-    if (rows == 8) {
-      if constexpr (H == 256) { if (hw) LAS_BWD(8, true, true); }
-      LAS_BWD(8, true, false);
-    }
+    if (rows == 4) LAS_BWD(4, false, H == 256);
+    if (rows == 8) LAS_BWD(8, true, H == 256);
     LAS_BWD(16, false, false);
   } else if constexpr (H == 128) {
-    if (rows == 4) { if (hw) LAS_BWD(4, false, true); LAS_BWD(4, false, false); }
-    if (rows == 8) { if (hw) LAS_BWD(8, false, true); LAS_BWD(8, false, false); }
+    if (rows == 4) LAS_BWD(4, false, true);
+    if (rows == 8) LAS_BWD(8, false, true);
     LAS_BWD(16, false, false);
   } else if constexpr (H == 64) {
     if (rows == 4) LAS_BWD(4, false, false);
@@ -1556,7 +1539,7 @@ extern "C" int las_lstm_slice_rows(int B, int H, int ndir) {
 extern "C" int las_lstm_fwd_workgroups(int B, int H, int ndir) {
   if (!supported_units(H) || B <= 0) return 0;
   const CoopGeom g = geom(B, H, ndir, false, slice_rows(B, H, ndir, false));
-  return g.blocks + (prefetch_mode() ? g.companions : 0);
+  return g.blocks + g.companions;
 }
 
 extern "C" size_t las_lstm_workspace_bytes(int B, int H, int ndir) {
@@ -1584,11 +1567,7 @@ int recurrent_fwd(float* xproj, const las_bf16* wpacked, const int32_t* length, 
   LAS_REQUIRE(supported_units(H), "las_lstm_recurrent_fwd: num_units %d not in {64,128,256,512,1024}", H);
   LAS_REQUIRE(workspace != nullptr && ((uintptr_t)workspace % 16 == 0), "las_lstm_recurrent_fwd: workspace missing or misaligned");
   hipStream_t st = (hipStream_t)stream;
-  int rc = 0;
-  if (!prefetch_mode()) {       // otherwise the companions clear the rows beyond each length
-    rc = las_check_hip(hipMemsetAsync(y, 0, (size_t)B * T * ndir * H * sizeof(las_bf16), st), "memset y");
-    if (rc) return rc;
-  }
+  // No memset of y: the prefetch companions clear the rows beyond each length.
   // No memset of the exchange buffer: the tags of a launch start from the launch base in the workspace header (see
   // launch_arrive); the caller zeroes the workspace ONCE, when it allocates it.  The first word of the header is the STICKY
   // timeout status (it survives until the host reads and clears it: one workspace serves every layer, forward and backward).
@@ -1653,12 +1632,7 @@ int recurrent_bwd(const float* gates, const float* cbuf, const float* dy, const 
   LAS_REQUIRE(supported_units(H), "las_lstm_recurrent_bwd: num_units %d not in {64,128,256,512,1024}", H);
   LAS_REQUIRE(workspace != nullptr && ((uintptr_t)workspace % 16 == 0), "las_lstm_recurrent_bwd: workspace missing or misaligned");
   hipStream_t st = (hipStream_t)stream;
-  int rc = 0;
-  if (!prefetch_mode()) {
-    rc = las_check_hip(hipMemsetAsync(dz, 0, (size_t)B * T * ndir * 4 * H * sizeof(las_bf16), st), "memset dz");
-    if (rc) return rc;
-  }
-  // (no memset of the exchange buffer: launch epochs, see las_lstm_recurrent_fwd)
+  // (no memset of dz or of the exchange buffer: companions and launch epochs, see las_lstm_recurrent_fwd)
   switch (H) {
     case 64: return launch_bwd<64>(gates, cbuf, dy, dc_last, dh_last, kh_bf16, length, dz, workspace, B, T, ndir, st);
     case 128: return launch_bwd<128>(gates, cbuf, dy, dc_last, dh_last, kh_bf16, length, dz, workspace, B, T, ndir, st);

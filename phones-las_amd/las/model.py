@@ -114,7 +114,7 @@ class Listener:
                 # starts on the other tensors while those products (which nothing else hides) are still running
                 self.before_bottom_grads = overlap.mark()
             res = ops.bilstm_backward(r, dy, st['d_state'] if l == len(recs) - 1 else None, grads, need_dx=(l > 0),
-                                      overlap=overlap, defer_weight_grads=defer, exposed=(l == 0 and overlap is not None and os.environ.get('LAS_TN_EXPOSED', '1') != '0'))
+                                      overlap=overlap, defer_weight_grads=defer, exposed=(l == 0 and overlap is not None))
             if defer:
                 st['dy'], st['deferred'] = res
             else:
@@ -306,7 +306,7 @@ class Speller:
         # rows [0, U) of `al2` are the alignments (this pass), rows [U, 2U) d(scores) (the backward pass); rows [0, U) of `cw2`
         # d(context) (the backward pass), rows [U, 2U) hW = h_t W_mem^T (formed beside the loss, off the critical path).  The
         # fp32 alignments share the row stride (struct las_dec_step has one lda for both).
-        merged = (self.att == hip.ATT_LUONG and os.environ.get('LAS_DMEM_MERGED', '1') != '0')
+        merged = self.att == hip.ATT_LUONG
         R = 2 if merged else 1
         align = torch.empty(B, R * U, Tmp, dtype=f32, device=dev)
         al2 = torch.empty(B, R * U, Tmp, dtype=bf, device=dev)

@@ -80,12 +80,11 @@ def check_all_lstm_status():
             raise hip.LasError('recurrent kernel (B=%d, H=%d) reported an inter-workgroup timeout (status %d)' % (B, H, st))
 
 
-# workgroups the fused weight-gradient product of a direction aims for (K slices x output tiles); LAS_TN_WGS overrides
-TN_WORKGROUPS = int(os.environ.get('LAS_TN_WGS', '704'))
+# workgroups the fused weight-gradient product of a direction aims for (K slices x output tiles)
+TN_WORKGROUPS = 704
 # ... of the bottom layer, whose two directions' products run ALONE on the chip (nothing hides them), at the same time on two
 # streams; a 512-thread workgroup with 96 KiB of LDS takes a CU
-TN_WORKGROUPS_EXPOSED = int(os.environ.get('LAS_TN_WGS_EXPOSED', '704'))
-TN_WIDE = os.environ.get('LAS_TN_WIDE', '1') != '0'         # (the library reads the same switch: 128 x 512 tiles of the fused product)
+TN_WORKGROUPS_EXPOSED = 704
 TN_SPLIT_WIDE = 0x10000                                      # LAS_TN_SPLIT_WIDE of las_hip.h: the tile shape travels in split_k
 
 
@@ -102,7 +101,7 @@ class Overlap:
         self.keep = []
 
     # how long side work that is going to run BESIDE a recurrent launch is held back (see fork)
-    BESIDE_US = int(os.environ.get('LAS_SIDE_DELAY_US', '12'))
+    BESIDE_US = 12
 
     def fork(self, *tensors, lane=0, beside_chain=False):
         """lane 1: another side stream, for two pieces of side work that should run at the same time (the two directions'
@@ -121,7 +120,7 @@ class Overlap:
             self.side2_busy = True
         side.wait_stream(torch.cuda.current_stream())
         self.keep.extend(tensors)
-        if beside_chain and self.BESIDE_US > 0:
+        if beside_chain:
             hip.check(hip.lib().las_stream_delay(self.BESIDE_US, side.cuda_stream))
         import contextlib
         ctx = contextlib.ExitStack()
@@ -179,10 +178,8 @@ FUSED_X = os.environ.get('LAS_LSTM_FUSED_X', '1') != '0'
 # layers; at 512 units the product beside the chain cost more than it hid: metric-L 17.83 against 17.69 ms): the product
 # (las_gemm_nt_stream) runs on a second stream BESIDE the recurrence and hands its rows over step block by step block.
 STREAM_X = os.environ.get('LAS_LSTM_STREAM', '1') != '0'
-STREAM_512 = os.environ.get('LAS_LSTM_STREAM_512', '0') != '0'      # (diagnostics: stream at 512 units too)
 STREAM_MIN_ROWS = int(os.environ.get('LAS_LSTM_STREAM_MIN_ROWS', '4096'))      # smaller products are not worth the hand-over
 STREAM_ALWAYS = os.environ.get('LAS_LSTM_STREAM_ALWAYS', '0') != '0'           # (diagnostics / tests: stream whatever the recurrence's length)
-STREAM_ROWS8_MIN_K = int(os.environ.get('LAS_STREAM_ROWS8_MIN_K', str(1 << 30)))      # (diagnostics, see _stream_setup)
 STREAM_MAX_WORKGROUPS = 192       # the recurrence (members + companions, a CU each) must leave CUs to the product beside it
 _PRODUCT_STREAMS = {}
 _ALIASED_STREAMS = []
@@ -339,7 +336,7 @@ def _stream_setup(a, lda, a_dir_stride, weights, xproj, sequence_length, B, T, H
     # chains leave (~0.28 PFLOP/s); beside a recurrence shorter than ~1.6 x that it is the recurrence that waits (metric-M's layer 2,
     # T = 400: 0.49 ms streamed against 0.33 + 0.14 one after the other since the image kernel; layer 1, T = 800: 0.79 against 0.84)
     long_enough = STREAM_ALWAYS or T * 0.835e-6 > 1.6 * (2.0 * B * T * nd * 4 * H * Dp) / 0.28e15
-    streamed = (STREAM_X and long_enough and (H == 256 or (H == 512 and STREAM_512)) and B * T >= STREAM_MIN_ROWS and lib.las_gemm_nt_stream_supported(nd * 4 * H, Dp, nd) == 1
+    streamed = (STREAM_X and long_enough and H == 256 and B * T >= STREAM_MIN_ROWS and lib.las_gemm_nt_stream_supported(nd * 4 * H, Dp, nd) == 1
                 and 16 % max(lib.las_lstm_slice_rows(B, H, nd), 1) == 0
                 and 0 < lib.las_lstm_fwd_workgroups(B, H, nd) <= STREAM_MAX_WORKGROUPS)
     if not streamed:
@@ -350,11 +347,6 @@ def _stream_setup(a, lda, a_dir_stride, weights, xproj, sequence_length, B, T, H
     # counters zeroed here, the product on its own stream (held back a few microseconds so that the chain's workgroups are
     # resident first), the recurrence consumes the rows as they become visible
     rows = lib.las_lstm_slice_rows(B, H, nd)
-    # (LAS_STREAM_ROWS8_MIN_K=k: 8-row chain slices under products with K >= k -- half the chain workgroups, more CUs for the
-    # product.  Measured in round 5, metric-M's layer 2 (K = 1024): 0.523 ms against 0.501 on 4-row slices, the step 6.08 against
-    # 6.05: the product beside the chain is not short of CUs.  Off by default.)
-    if rows == 4 and Dp >= STREAM_ROWS8_MIN_K:
-        rows = 8
     n = lib.las_gemm_nt_stream_flags(B, T, nd, rows)
     ready = weights.__dict__.setdefault('_ready', {}).get((B, T, rows))
     if ready is None:
@@ -505,10 +497,6 @@ def concat_outputs(outputs):
     return outputs
 
 
-# LAS_MASKED_DX=0: the input-dropout backward as its own pass over two partial dX buffers again (diagnostics, A/B timing)
-MASKED_DX = os.environ.get('LAS_MASKED_DX', '1') != '0'
-
-
 def bilstm_backward(rec, dy, d_state, grads, need_dx=True, overlap=None, defer_weight_grads=False, exposed=False):
     """Reverse-mode AD of one bilstm() call.  dy [B,T,nd*H] fp32 (gradient of the concatenated outputs),
     d_state: None or (dc_last, dh_last) each [nd,B,H] fp32.  Accumulates into ``grads`` (name -> fp32
@@ -541,7 +529,7 @@ def bilstm_backward(rec, dy, d_state, grads, need_dx=True, overlap=None, defer_w
         # fused product: about 700 workgroups in flight measured best on MI355X (128 x 128 output tiles, K cut in slices)
         tiles = -(-(Df + H + 1) // 128) * -(-(4 * H) // 128)
         split = max(1, min(32, BT // 512, round((TN_WORKGROUPS_EXPOSED if exposed else TN_WORKGROUPS) / tiles)))
-        wide = TN_WIDE and (4 * H) % 512 == 0 and (exposed or H >= 512)
+        wide = (4 * H) % 512 == 0 and (exposed or H >= 512)
         if wide:                                 # 128 x 512 output tiles (round 5): half the workgroups per K slice, so twice the slices
             split = max(1, min(32, BT // 512, 2 * split))
     keepalive = [dz, x, y] + [a for a, _ in (dropped or [])]
@@ -602,7 +590,7 @@ def bilstm_backward(rec, dy, d_state, grads, need_dx=True, overlap=None, defer_w
             # the counter-based generator); summed when both directions read the same input, side by side otherwise
             parts = []
             lib = hip.lib()
-            if keep < 1.0 and not split_in and nd == 2 and BT > 64 and D > 64 and MASKED_DX:
+            if keep < 1.0 and not split_in and nd == 2 and BT > 64 and D > 64:
                 # both directions read the same input through their own masks: dX = sum_d mask_d * (dZ_d K_x,d^T) / keep, the
                 # mask applied in the products' epilogues (the first stores, the second accumulates)
                 seed, stream0 = rec['rng']

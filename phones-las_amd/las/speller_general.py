@@ -586,7 +586,7 @@ class GeneralSpeller:
             p.wprojT, p.ldw, p.bproj = hip.addr(self.wprojT), self.P, hip.addr(self.bproj)
             p.logits, p.ld_logits, p.plog, p.V, p.Vp = 0, U * Vp, hip.addr(plog), self.V, Vp
         p.U, p.K_in = U, Kp
-        if self.uses_wq and self.wq_pkT is not None and Hd in (128, 256) and os.environ.get('LAS_DEC_PQ_MFMA', '1') != '0':
+        if self.uses_wq and self.wq_pkT is not None and Hd in (128, 256):
             p.wq_packed = hip.addr(self.wq_pkT)
         p.inc_tok, p.inc_cprev, p.inc_gates, p.inc_cout, p.inc_h, p.inc_h2 = 1, Hd, 4 * Hd, Hd, Hd, Kp
         p.inc_align, p.inc_pq, p.inc_ctx, p.inc_ctx2, p.inc_p = Tmp, Hd, M, Kp, Tmp
@@ -767,11 +767,10 @@ class GeneralSpeller:
             if self.has_al:
                 q.datt_out, q.ld_datt = hip.addr(datt_bf), U * A
                 q.waln_packed = hip.addr(self.waln_pk)
-                if os.environ.get('LAS_DEC_SEQ_VW', '1') != '0':
-                    # VW = values W_c [B, T', A]: d(alignments)_t = VW d(attention_t) inside the launch (no pass over the values)
-                    vw = torch.empty(B, Tm, A, dtype=f32, device=dev)
-                    hip.gemm_nt(sv['memory'], self.walT[:, Hd:], vw, B * Tm, A, M, lda=M, ldb=Hd + M, ldc=A)
-                    q.vw, q.ld_vw = hip.addr(vw), Tm * A
+                # VW = values W_c [B, T', A]: d(alignments)_t = VW d(attention_t) inside the launch (no pass over the values)
+                vw = torch.empty(B, Tm, A, dtype=f32, device=dev)
+                hip.gemm_nt(sv['memory'], self.walT[:, Hd:], vw, B * Tm, A, M, lda=M, ldb=Hd + M, ldc=A)
+                q.vw, q.ld_vw = hip.addr(vw), Tm * A
             q.kn_packed = hip.addr(self.kn_pk)
             if bah or self.mono:                    # d(attention_v) / d(score_bias): fixed-order sums instead of atomics
                 q.sum_workspace = hip.addr(self._persist_workspace('sum', lib.las_decoder_sum_workspace_bytes(32 * ((B + 7) // 8), Hd + 1)))

@@ -597,8 +597,7 @@ class LasModel:
         self.world_size = world_size
         self.process_group = process_group
         self._images_stale = False
-        # LAS_SERIAL=1 (diagnostics, A/B timing): no side streams -- every product runs where it is issued, on the one stream
-        self.overlap = las_model.ops.Overlap() if os.environ.get('LAS_SERIAL', '0') != '1' else las_model.ops._NoOverlap()
+        self.overlap = las_model.ops.Overlap()
         self.tail_buckets = self._tail_buckets()
 
     def _tail_buckets(self):
@@ -629,7 +628,7 @@ class LasModel:
         recurrence (which leaves a third of the CUs idle); wait() makes the current stream wait for it in front of the
         second layer.  Otherwise everything on the current stream; returns None."""
         hooks = None
-        if beside_first_layer and len(self.listener.layers) > 1 and os.environ.get('LAS_REFRESH_BESIDE', '1') != '0':
+        if beside_first_layer and len(self.listener.layers) > 1:
             self.listener.refresh(self.vars.params, layers=[0])
             done = []
 

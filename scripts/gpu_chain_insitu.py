@@ -1,5 +1,5 @@
 # Per-launch durations of the recurrent kernels inside real train steps (HIP events around each launch, eager launches), next to
-# the stand-alone loop of scripts/gpu_lstm_time.py.  usage: [LAS_SERIAL=1 LAS_LSTM_STREAM=0] python scripts/gpu_chain_insitu.py [config] [steps]
+# the stand-alone loop of scripts/gpu_lstm_time.py.  usage: [LAS_LSTM_STREAM=0] python scripts/gpu_chain_insitu.py [config] [steps]
 import sys, torch
 sys.path.insert(0, '.')
 import bench

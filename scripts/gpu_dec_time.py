@@ -1,5 +1,5 @@
-# times one fused decoder step (forward) alone, captured 100x in a graph: LAS_DEC_STREAM=0/1, varying memory length
-import os, sys, ctypes as C, torch
+# times one fused decoder step (forward) alone, captured 100x in a graph, varying memory length
+import sys, ctypes as C, torch
 sys.path.insert(0, '.')
 from phones_las_amd import hip
 lib = hip.lib()
@@ -46,5 +46,5 @@ for Tm, parts in ((200, 4), (200, 1), (200, 2), (200, 8), (48, 4), (8, 4)):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(); g.replay(); e1.record(); torch.cuda.synchronize()
         ts.append(e0.elapsed_time(e1) * 10.0)
-    print('stream=%s Tm %3d parts %d: %.1f us per step   ctx checksum %.5f' % (os.environ.get('LAS_DEC_STREAM', '1'), Tm, parts, min(ts),
+    print('Tm %3d parts %d: %.1f us per step   ctx checksum %.5f' % (Tm, parts, min(ts),
                                                                              float(ctx.float().abs().mean())))

@@ -47,4 +47,4 @@ print('needed HBM traffic %.1f MB in %.2f ms = %.1f GB/s = %.4f of the 8 TB/s ro
 # the arithmetic the stages need: the 320-point direct DFT (re and im: 4 flops per sample and bin) + the mel filterbank, fp32
 flops = frames * (320 * 161 * 4 + 161 * 40 * 2)
 print('arithmetic %.1f GF in %.2f ms (all three launches) >= %.1f TFLOP/s = %.3f of the 157 TFLOP/s fp32 (vector = matrix) roof; '
-      'round 3 (one frame per workgroup, tables re-read per frame: LAS_FE_BLOCKED=0): 4.8 ms' % (flops / 1e9, t_batch * 1e3, flops / t_batch / 1e12, flops / t_batch / 157e12))
+      'round 3 (one frame per workgroup, tables re-read per frame): 4.8 ms' % (flops / 1e9, t_batch * 1e3, flops / t_batch / 1e12, flops / t_batch / 157e12))

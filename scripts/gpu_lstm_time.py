@@ -1,4 +1,4 @@
-# times the recurrent forward/backward kernels alone (layer shapes of metric-M); LAS_LSTM_PREFETCH selects the mode
+# times the recurrent forward/backward kernels alone (layer shapes of metric-M)
 import os, sys, torch
 sys.path.insert(0, '.')
 from phones_las_amd import hip
@@ -48,6 +48,6 @@ for T in (800, 400, 200):
         e[2].record(); torch.cuda.synchronize()
         ops.check_lstm_status(B, H, nd)
         tf.append(e[0].elapsed_time(e[1])); tb.append(e[3].elapsed_time(e[2]))
-    print('H %d T %d mode %s: fwd %.3f ms (%.2f us/step)  bwd %.3f ms (%.2f us/step)  checksum %.6f %.6f' % (
-        H, T, os.environ.get('LAS_LSTM_PREFETCH', 'default'), min(tf), min(tf) * 1e3 / T, min(tb), min(tb) * 1e3 / T,
+    print('H %d T %d: fwd %.3f ms (%.2f us/step)  bwd %.3f ms (%.2f us/step)  checksum %.6f %.6f' % (
+        H, T, min(tf), min(tf) * 1e3 / T, min(tb), min(tb) * 1e3 / T,
         float(y.float().abs().mean()), float(dz.float().abs().mean())))

@@ -222,8 +222,8 @@ def test_gemm_tn_lstm_fused_weight_gradients(D, H, B, T, shift, use_ws, wide):
 def test_gemm_nt_ring_asymmetric_identity_strides_and_batch():
     """The LDS-DMA ring kernel (gemm_nt_ring_kernel: 256 x 128 tiles of v_mfma_f32_32x32x16_bf16): A = I against an
     asymmetric B catches a transposed or permuted C write and a wrong source-chunk swizzle exactly (integer data);
-    sub-matrix views through lda / ldb / ldc; a batch of two; and the same product through the register-staged kernel
-    (LAS_GEMM_RING is read once per process, so the reference here is the float64 product)."""
+    sub-matrix views through lda / ldb / ldc; a batch of two.  (The shape alone picks the kernel, so the reference here is
+    the float64 product.)"""
     from phones_las_amd import hip
     n = 1024
     A = torch.eye(n).to(torch.bfloat16).cuda()
