@@ -452,7 +452,9 @@ __device__ __forceinline__ void dec_step_fwd_body(const las_dec_step& s, const i
       };
       if constexpr (RES) run((lds_cu16)ph->lkeys, f0);
       else run(keys, 0);
-    } else if (Hd <= 32 * KMAX) {
+    } else if (Hd <= 32 * KMAX && Hd % 32 == 0) {
+      // (a width that is no multiple of 32 takes the rolled loop below, which walks 8 units at a time: Hd / 32 pieces per lane
+      //  left the last Hd % 32 units out of every score -- all of them at 24 units)
       const int nk = Hd / 32;                          // loads per lane and frame
       // krows: key rows from memory (row 0 = frame 0) or from the workgroup's LDS copy (row 0 = frame f0)
       auto score_pass = [&](auto krows, int row0) {
