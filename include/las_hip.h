@@ -486,7 +486,31 @@ typedef struct las_dec_persist {
   const las_bf16* emb;
   int64_t ld_emb;
   int32_t T0, reserved_t0;
+  /* Free-running greedy decoding (GreedyEmbeddingHelper, las/model.py:270-274,337-347), greedy != 0;
+   * las_decoder_persist_greedy_supported.  The scheduled-sampling phase without its noise, for every utterance at every step:
+   * after step t the launch forms logits_t = out_t W_proj + b, writes the row (fp32, columns [V, Vp) zero) to
+   * logits[b*ld_logits + t*Vp ..], takes the first-index argmax over v < V, writes it to sample_ids[b*ld_samples + t] and --
+   * while t + 1 < U -- to s.tok_ids[b*tok_stride + t+1] (inc_tok must be 1; with `emb` the token's embedded row goes into
+   * the operand row of step t+1), sets final_len[b] = t + 1 while finished[b] is 0 and then finished[b] |= (argmax == eos_id).
+   * `unfinished` (optional) is decremented once per utterance when its finished word is set: the host hands it over
+   * holding the number of utterances whose finished word is 0.
+   * The launch runs the step window [step_begin, step_end) inside buffers of capacity U (both 0: all of [0, U)); every per-step
+   * address stays indexed by t.  A window starts from what step step_begin - 1 left behind: the state row s.c_prev (c1 / h1), the
+   * operand row x[b, step_begin], tok_ids[b, step_begin], finished[b], final_len[b]; its last step writes the next operand row
+   * and token unless it is step U - 1.  plog is [step_end - step_begin, B, 4, Vp] here (indexed by t - step_begin).
+   * sampling_prob must be 0 and s.drop_keep 1. */
+  int32_t greedy, eos_id;
+  int32_t* sample_ids;
+  int64_t ld_samples;
+  int32_t* finished;             /* [B] int32, in / out */
+  int32_t* final_len;            /* [B] int32, in / out */
+  int32_t* unfinished;           /* optional device word, in / out */
+  int32_t step_begin, step_end;
 } las_dec_persist;
+/* 1 for the shapes the greedy instantiations are built for: softmax normaliser, Luong / Bahdanau, decoder_units 128 or 256, no
+ * attention layer (A = 0), Vp <= 1024; one cell (K1_in = 0; wiring ignored) or two cells in wiring 0 / 1 (K1_in as for
+ * las_decoder_persist2_supported); K_in / M as for las_decoder_persist_supported. */
+int las_decoder_persist_greedy_supported(int Hd, int M, int K_in, int K1_in, int attention, int norm, int wiring, int A, int Vp);
 int las_decoder_persist_supported(int Hd, int M, int K_in, int attention, int norm);   /* 1 if the shapes fit */
 int las_decoder_persist2_supported(int Hd, int M, int K_in, int K1_in, int attention, int wiring);   /* ... with a second cell */
 /* ... with an attention layer of A outputs (A = 0: none) and / or a monotonic normaliser (decoder_units 128 / 256) */

@@ -39,7 +39,7 @@ extern "C" int las_set_knob(const char* name, int value) {
 // 103: las_resample_batch (csrc/resample.hip: resampy 0.2.2 kaiser_best over a ragged batch, audio.py) added, nothing else changed;
 // 101 (round 6): host.cpp split off, the recurrent backward launches eight-wave workgroups at 64 / 128 / 256 units (same entry points,
 // same results); 100 (round 5) removed five entry points and gave las_lstm_fwd::reserved1 a meaning (rows_per_slice).
-extern "C" int las_version(void) { return 104; }
+extern "C" int las_version(void) { return 105; }
 
 namespace {
 

@@ -858,6 +858,46 @@ __device__ bool persist_barrier(pu64* flags, int member, unsigned epoch, bool lo
   return *lds_fail == 0;
 }
 
+// Sampling phase of the one-launch forward kernels (compile-time): none, scheduled sampling (TRAIN), free-running greedy decoding
+constexpr int P_SAMPLE_OFF = 0, P_SAMPLE_SCHEDULED = 1, P_SAMPLE_GREEDY = 2;
+
+// Greedy decoding, part 0 of utterance b after step t (all 256 threads; lg [Vp] in LDS: the logits row, columns [V, Vp) zero):
+// the row to memory, its argmax over v < V -- strict > per lane over ascending v, then the lowest index among equal values
+// across the lanes: tf.argmax's first index --, the sample, the token fed at step t+1, and the finished / length words in the
+// order of GreedyEmbeddingHelper's caller (the length moves while the utterance is unfinished, THEN </s> finishes it).
+// Returns the token in wave 0.
+__device__ __forceinline__ int greedy_emit(const las_dec_persist& p, const float* lg, const int b, const int t) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  float* lrow = p.logits + (int64_t)b * p.ld_logits + (int64_t)t * p.Vp;
+  for (int v = tid; v < p.Vp; v += 256) lrow[v] = lg[v];
+  int arg = 0;
+  if (tid < 64) {
+    float best = -INFINITY;
+    for (int v = lane; v < p.V; v += 64) {
+      const float x = lg[v];
+      if (x > best) { best = x; arg = v; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ob = __shfl_xor(best, o, 64);
+      const int oa = __shfl_xor(arg, o, 64);
+      if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
+    }
+    if (lane == 0) {
+      p.sample_ids[(int64_t)b * p.ld_samples + t] = arg;
+      if (t + 1 < p.U) const_cast<int32_t*>(p.s.tok_ids)[(int64_t)b * p.s.tok_stride + t + 1] = arg;
+      if (p.finished[b] == 0) {
+        p.final_len[b] = t + 1;
+        if (arg == p.eos_id) {
+          p.finished[b] = 1;
+          if (p.unfinished) atomicAdd(p.unfinished, -1);
+        }
+      }
+    }
+  }
+  return arg;
+}
+
 // NTL_MAX 16-column tiles of z per member (4 Hd / 32 / 16) and KCW_MAX 32-deep K chunks per wave (K_in / 32 / 4) stay in
 // registers as MFMA B fragments: <2, 12> for decoder_units <= 256 (96 VGPRs), <4, 20, 8> for 512 units with a 2048-deep
 // memory
@@ -875,9 +915,10 @@ __device__ bool persist_barrier(pu64* flags, int member, unsigned epoch, bool lo
 // gathered chunk by chunk from where its pieces already lie (h0_t in s.h_out, attention_t in s.ctx_out, attention_{t-1} in the
 // operand row of cell 0, h1_{t-1} in p.h1): no copies; K1's chunks are streamed from L2 at every step (at 2M + Hd columns in
 // the --bottom_only wiring they would not fit the registers next to K0's).
-template <bool SAMPLING, bool RES, int NTL_MAX = 2, int KCW_MAX = 12, int KRES = KCW_MAX, bool AL = false, int KAL_MAX = 10, bool TWO = false>
+template <int SMODE, bool RES, int NTL_MAX = 2, int KCW_MAX = 12, int KRES = KCW_MAX, bool AL = false, int KAL_MAX = 10, bool TWO = false>
 __global__ __launch_bounds__(256) void dec_persist_fwd_kernel(las_dec_persist p) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
+  constexpr bool SAMPLING = SMODE == P_SAMPLE_SCHEDULED, GREEDY = SMODE == P_SAMPLE_GREEDY;
   const las_dec_step& s0 = p.s;
   const int B = s0.B, Hd = s0.Hd, M = s0.M, Tm = s0.Tm;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, lq = lane >> 4;
@@ -981,7 +1022,8 @@ __global__ __launch_bounds__(256) void dec_persist_fwd_kernel(las_dec_persist p)
 #pragma unroll
     for (int g = 0; g < 4; ++g) bias4[g] = s0.bias[g * Hd + tid];
 
-  for (int t = 0; t < p.U; ++t) {
+  const int t_begin = GREEDY ? p.step_begin : 0, t_end = GREEDY ? p.step_end : p.U;     // (greedy: a step window of the capacity U)
+  for (int t = t_begin; t < t_end; ++t) {
     // the S role's cell operands that are already final (token id of this step -- teacher's, or drawn before the last
     // barrier --, its kernel row, c_{t-1}): requested now, used after the product and its barrier
     int tok_pre = 0;
@@ -1293,6 +1335,52 @@ __global__ __launch_bounds__(256) void dec_persist_fwd_kernel(las_dec_persist p)
       }
       }
     }
+    if constexpr (GREEDY) {
+      // ---- free-running greedy decoding (GreedyEmbeddingHelper): the phase above without its draws, for EVERY utterance at
+      //      EVERY step, the last one included: the four parts' partial projection products, then part 0 keeps the logits row,
+      //      takes its first-index argmax and records sample, fed token and the finished / length words ----
+      const int V = p.V, Vp = p.Vp;
+      const bool mine = bs < B;
+      float* plog_t = p.plog + ((int64_t)(t - t_begin) * B + (mine ? bs : 0)) * 4 * Vp;
+      if (mine) {
+        const bool out_h1 = TWO && p.wiring == 1;         // the decoder's output row: the context, or h1_t (see above)
+        const int cols = (out_h1 ? Hd : M) / 4, c0 = part * cols;
+        float* cx = out_h1 ? sm + c0 : sm;
+        __builtin_amdgcn_s_waitcnt(0x0070);               // my context stores are done
+        __syncthreads();
+        if (!out_h1) {
+          const unsigned short* crow = s0.ctx_out + (int64_t)bs * s0.ldc + (int64_t)t * p.inc_ctx + c0;
+          for (int c = tid; c < cols; c += 256)
+            cx[c] = las_bf2f(__builtin_bit_cast(unsigned short, (unsigned short)__hip_atomic_load(
+                        reinterpret_cast<const unsigned short*>(crow) + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)));
+          __syncthreads();
+        }
+        for (int v = tid; v < Vp; v += 256) {
+          float acc = 0.f;
+          if (v < V) {
+            const unsigned short* wrow = p.wprojT + (int64_t)v * p.ldw + c0;
+            for (int c = 0; c < cols; c += 8) {
+              const uint4 w = *reinterpret_cast<const uint4*>(wrow + c);
+              acc += dot8(w, cx + c);
+            }
+          }
+          plog_t[part * Vp + v] = acc;
+        }
+      }
+      if (!persist_barrier(flags, member, ++epoch, local, fail)) break;
+      if (mine && part == 0) {
+        float* lg = sm;                                   // [Vp]
+        for (int v = tid; v < Vp; v += 256)
+          lg[v] = v < V ? plog_t[v] + plog_t[Vp + v] + plog_t[2 * Vp + v] + plog_t[3 * Vp + v] + p.bproj[v] : 0.f;
+        __syncthreads();
+        const int out = greedy_emit(p, lg, bs, t);        // (the token: in wave 0)
+        if constexpr (TWO) {
+          if (p.emb && tid < 64 && t + 1 < p.U)           // dense token feed: the token's embedded row into the next operand row
+            for (int c = lane; c < p.T0; c += 64)
+              const_cast<unsigned short*>(p.x)[(int64_t)bs * p.ldx + (int64_t)(t + 1) * p.inc_x + c] = p.emb[(int64_t)out * p.ld_emb + c];
+        }
+      }
+    }
     if constexpr (AL) {
       // ---- A: attention_t = [h_t | context_t] W_al for the group's utterances (every part's context columns and h_t are
       //      in memory behind this barrier; their lines were never read by this workgroup before) ----
@@ -1398,9 +1486,10 @@ __device__ __forceinline__ float dot2_bf16(unsigned a, unsigned b, float acc) {
 
 // NTL: 16-column tiles of z per member (decoder_units / 128: 1, 2 or 4).  KRES of the KCWM 32-deep K chunks a wave owns stay in
 // registers as MFMA B fragments; the chunks beyond (512 units: 12 of 20) are streamed from L2 at every step, three in flight.
-template <int ATT, int NTL, int KRES = 12, int KCWM = 12, bool SAMPLING = false>
+template <int ATT, int NTL, int KRES = 12, int KCWM = 12, int SMODE = P_SAMPLE_OFF>
 __global__ __launch_bounds__(256) void dec_persist_fwd_lean_kernel(las_dec_persist p) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
+  constexpr bool SAMPLING = SMODE == P_SAMPLE_SCHEDULED, GREEDY = SMODE == P_SAMPLE_GREEDY;
   constexpr int UPT = NTL == 4 ? 2 : 1;                    // hidden units per thread (512 units: tid and tid + 256)
   constexpr int NK = NTL * 4;                              // 16-byte key pieces per lane and frame (4 lanes per frame)
   const int B = p.s.B, Hd = p.s.Hd, M = p.s.M, Tm = p.s.Tm, U = p.U;
@@ -1502,11 +1591,15 @@ __global__ __launch_bounds__(256) void dec_persist_fwd_lean_kernel(las_dec_persi
   }
   // the fed token ids of all steps (the teacher's: known up front).  From LDS the next step's id costs an LDS read; as a global
   // load it was waited for at once (a workgroup-uniform value goes to a scalar register): an L2 round trip in every step
-  for (int i = tid; i < U; i += 256) ltok[i] = p.s.tok_ids[(int64_t)bsc * p.s.tok_stride + (int64_t)i * p.inc_tok];
+  // (greedy decoding produces the tokens itself: every part reads the next one from memory behind the step's barrier)
+  if constexpr (!GREEDY)
+    for (int i = tid; i < U; i += 256) ltok[i] = p.s.tok_ids[(int64_t)bsc * p.s.tok_stride + (int64_t)i * p.inc_tok];
+  // greedy: a step window [t_begin, t_end) of the capacity U, from the state step t_begin - 1 left in the buffers
+  const int t_begin = GREEDY ? p.step_begin : 0, t_end = GREEDY ? p.step_end : U;
   unsigned epoch = 0;
   const bool unit = tid < Hd && have;                      // this thread owns hidden units tid (+ 256) of utterance bs
   float bias4[UPT][4], c_reg[UPT];
-  int tok_cur = p.s.tok_ids[(int64_t)bsc * p.s.tok_stride];          // (every thread: the loads of the loop are unconditional)
+  int tok_cur = p.s.tok_ids[(int64_t)bsc * p.s.tok_stride + (GREEDY ? t_begin : 0)];   // (every thread: the loads of the loop are unconditional)
 #pragma unroll
   for (int q = 0; q < UPT; ++q) {
     c_reg[q] = 0.f;
@@ -1515,7 +1608,7 @@ __global__ __launch_bounds__(256) void dec_persist_fwd_lean_kernel(las_dec_persi
     if (unit) {
 #pragma unroll
       for (int g = 0; g < 4; ++g) bias4[q][g] = p.s.bias[g * Hd + tid + q * 256];
-      c_reg[q] = p.s.c_prev[(int64_t)bs * p.s.ldcp + tid + q * 256];
+      c_reg[q] = p.s.c_prev[(int64_t)bs * p.s.ldcp + (GREEDY ? (int64_t)t_begin * p.inc_cprev : 0) + tid + q * 256];
     }
   }
   const float keep = p.s.drop_keep;
@@ -1526,7 +1619,7 @@ __global__ __launch_bounds__(256) void dec_persist_fwd_lean_kernel(las_dec_persi
   pu64* const xpqb = xzb + 2 * (size_t)B * 4 * Hd;          // [2][B][Hd]: the four quarters of the processed query (Bahdanau)
   __syncthreads();
 
-  for (int t = 0; t < U; ++t) {
+  for (int t = t_begin; t < t_end; ++t) {
     LAS_STAMP(t, 0);
     const bool last = (t + 1 == U);
     const unsigned xtag = (unsigned)(t + 1);
@@ -1624,7 +1717,7 @@ __global__ __launch_bounds__(256) void dec_persist_fwd_lean_kernel(las_dec_persi
       }
     }
     LAS_STAMP(t, 2);
-    const int tok_next = ltok[min(t + 1, U - 1)];            // the next step's token id
+    const int tok_next = GREEDY ? tok_cur : ltok[min(t + 1, U - 1)];      // the next step's token id (greedy: read behind the barrier)
 
     // ---- S: cell + attention of utterance bs, frames / context columns of `part` ----
     if (have) {
@@ -1932,7 +2025,7 @@ __global__ __launch_bounds__(256) void dec_persist_fwd_lean_kernel(las_dec_persi
           if (j < ncols) {
             const unsigned short o = las_f2bf(cv);
             p.s.ctx_out[(int64_t)bs * p.s.ldc + (int64_t)t * p.inc_ctx + c_begin + j] = o;
-            if constexpr (SAMPLING) cred[j] = las_bf2f(o);   // (the sampling phase's operand: the context as the projection sees it)
+            if constexpr (SAMPLING || GREEDY) cred[j] = las_bf2f(o);   // (the sampling phase's operand: the context as the projection sees it)
             if (!last) {
               unsigned short o2 = o;
               if (keep < 1.0f) {   // the copy that feeds step t+1's cell goes through that step's input dropout
@@ -2026,10 +2119,63 @@ __global__ __launch_bounds__(256) void dec_persist_fwd_lean_kernel(las_dec_persi
         resampled = my_sel;
       }
     }
+    if constexpr (GREEDY) {
+      // ---- free-running greedy decoding: the phase above without its draws, for EVERY utterance at EVERY step (the last one
+      //      included): partial projection products of the four parts, then part 0 keeps the logits row, takes its first-index
+      //      argmax and records sample, fed token and the finished / length words (greedy_emit) ----
+      const int V = p.V, Vp = p.Vp;
+      float* plog_t = p.plog + ((int64_t)(t - t_begin) * B + bsc) * 4 * Vp;
+      if (have) {
+        const float* cx = cred;                           // [ncols] my context columns (bf16 values), left there by the context phase
+        __syncthreads();
+        if (V <= 64 && (ncols & 31) == 0) {               // 64 rows x 4 column quarters, as above
+          const int v = tid & 63, q = tid >> 6, qn = ncols >> 2;
+          float acc = 0.f;
+          if (v < V) {
+            const unsigned short* wrow = p.wprojT + (int64_t)v * p.ldw + c_begin + q * qn;
+            for (int c0 = 0; c0 < qn; c0 += 64) {
+              uint4 w[8];
+#pragma unroll
+              for (int i = 0; i < 8; ++i) w[i] = c0 + i * 8 < qn ? *reinterpret_cast<const uint4*>(wrow + c0 + i * 8) : make_uint4(0, 0, 0, 0);
+#pragma unroll
+              for (int i = 0; i < 8; ++i)
+                if (c0 + i * 8 < qn) acc += dot8(w[i], cx + q * qn + c0 + i * 8);
+            }
+          }
+          cred[1024 + tid] = acc;
+          __syncthreads();
+          if (tid < Vp) plog_t[part * Vp + tid] = tid < V ? (cred[1024 + tid] + cred[1088 + tid]) + (cred[1152 + tid] + cred[1216 + tid]) : 0.f;
+        } else {
+          for (int v = tid; v < Vp; v += 256) {
+            float acc = 0.f;
+            if (v < V) {
+              const unsigned short* wrow = p.wprojT + (int64_t)v * p.ldw + c_begin;
+              for (int c = 0; c < ncols; c += 8) {
+                const uint4 w = *reinterpret_cast<const uint4*>(wrow + c);
+                acc += dot8(w, cx + c);
+              }
+            }
+            plog_t[part * Vp + v] = acc;
+          }
+        }
+      }
+      if (!persist_barrier(flags, member, ++epoch, local, fail)) break;
+      if (have && part == 0) {
+        float* lg = cred;                                 // [Vp]
+        for (int v = tid; v < Vp; v += 256)
+          lg[v] = v < V ? plog_t[v] + plog_t[Vp + v] + plog_t[2 * Vp + v] + plog_t[3 * Vp + v] + p.bproj[v] : 0.f;
+        __syncthreads();
+        greedy_emit(p, lg, bs, t);
+      }
+    }
     if (!persist_barrier(flags, member, ++epoch, local, fail)) break;
     if constexpr (SAMPLING) {
       // the token part 0 has just drawn for step t+1 (behind the barrier: every part of the utterance reads it)
       if (resampled) tok_cur = __hip_atomic_load(p.s.tok_ids + (int64_t)bs * p.s.tok_stride + t + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if constexpr (GREEDY) {
+      // the token part 0 has just chosen for step t+1: never from the LDS table, which holds what the launch was handed
+      if (have && t + 1 < U) tok_cur = __hip_atomic_load(p.s.tok_ids + (int64_t)bs * p.s.tok_stride + t + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     LAS_STAMP(t, 10);
   }
@@ -4189,6 +4335,19 @@ extern "C" int las_decoder_persist_supported(int Hd, int M, int K_in, int attent
   return 1;
 }
 
+extern "C" int las_decoder_persist_greedy_supported(int Hd, int M, int K_in, int K1_in, int attention, int norm, int wiring, int A, int Vp) {
+  // free-running greedy decoding inside the launch: the shapes its instantiations are built for (one cell: the lean kernel, or
+  // the general body where the lean kernel's LDS layout does not fit; two cells: the general body, either wiring)
+  if (norm != LAS_NORM_SOFTMAX) return 0;
+  if (attention != LAS_ATT_LUONG && attention != LAS_ATT_BAHDANAU) return 0;
+  if (Hd != 128 && Hd != 256) return 0;
+  if (A != 0) return 0;                                    // no attention layer
+  if (Vp < 1 || Vp > 1024) return 0;                       // the logits row in LDS
+  if (K_in % 64 != 0 || K_in / 32 > 48 || M % 32 != 0) return 0;
+  if (K1_in == 0) return 1;
+  return las_decoder_persist2_supported(Hd, M, K_in, K1_in, attention, wiring);
+}
+
 // Every workgroup of a persistent launch needs a CU of its own (its registers and LDS fill one) and the 32 of a group must
 // be resident together: 8 utterances per 32 CUs, 64 at once on a 256-CU MI355X.  Blocks are laid out in chunks of 8 groups,
 // so a larger batch (up to four chunks per launch) runs chunk after chunk as CUs become free.
@@ -4237,6 +4396,35 @@ extern "C" int las_decoder_persist_fwd(const las_dec_persist* p, void* stream) {
   LAS_REQUIRE(p->sampling_prob <= 0.f || (p->wprojT && p->bproj && p->plog && p->V > 0 && p->Vp >= p->V &&
                                           p->Vp <= 1024 && s->M % 32 == 0 && p->inc_tok == 1),
               "las_decoder_persist_fwd: scheduled sampling needs wprojT, bproj, plog (and fed ids with unit step)");
+  const bool greedy = p->greedy != 0;
+  las_dec_persist pw;
+  if (greedy) {
+    LAS_REQUIRE(las_decoder_persist_greedy_supported(s->Hd, s->M, p->K_in, two ? p->K1_in : 0, s->attention, s->norm, p->wiring,
+                                                     p->walT ? p->A : 0, p->Vp) && (two || s->tok_rows),
+                "las_decoder_persist_fwd: greedy: configuration not supported (Hd=%d M=%d K_in=%d K1_in=%d attention=%d norm=%d A=%d Vp=%d)",
+                s->Hd, s->M, p->K_in, two ? p->K1_in : 0, s->attention, s->norm, p->walT ? p->A : 0, p->Vp);
+    LAS_REQUIRE(p->sampling_prob <= 0.f, "las_decoder_persist_fwd: greedy excludes scheduled sampling (sampling_prob must be 0)");
+    LAS_REQUIRE(s->drop_keep >= 1.0f, "las_decoder_persist_fwd: greedy excludes input dropout (drop_keep must be 1)");
+    LAS_REQUIRE(p->logits && p->ld_logits >= (int64_t)p->U * p->Vp, "las_decoder_persist_fwd: greedy needs logits (ld_logits >= U * Vp)");
+    LAS_REQUIRE(p->sample_ids && p->ld_samples >= p->U, "las_decoder_persist_fwd: greedy needs sample_ids (ld_samples >= U)");
+    LAS_REQUIRE(p->finished, "las_decoder_persist_fwd: greedy needs finished");
+    LAS_REQUIRE(p->final_len, "las_decoder_persist_fwd: greedy needs final_len");
+    LAS_REQUIRE(p->wprojT, "las_decoder_persist_fwd: greedy needs wprojT");
+    LAS_REQUIRE(p->ldw >= ((two && p->wiring == 1) ? s->Hd : s->M), "las_decoder_persist_fwd: greedy: ldw below the output width");
+    LAS_REQUIRE(p->bproj, "las_decoder_persist_fwd: greedy needs bproj");
+    LAS_REQUIRE(p->plog, "las_decoder_persist_fwd: greedy needs plog");
+    LAS_REQUIRE(p->V > 0 && p->Vp >= p->V, "las_decoder_persist_fwd: greedy needs 0 < V <= Vp");
+    LAS_REQUIRE(p->eos_id >= 0 && p->eos_id < p->V, "las_decoder_persist_fwd: greedy: eos_id outside [0, V)");
+    LAS_REQUIRE(p->inc_tok == 1, "las_decoder_persist_fwd: greedy writes the fed ids: inc_tok must be 1");
+    LAS_REQUIRE(s->tok_ids, "las_decoder_persist_fwd: greedy needs tok_ids");
+    const bool whole = p->step_begin == 0 && p->step_end == 0;
+    LAS_REQUIRE(whole || (p->step_begin >= 0 && p->step_begin < p->step_end && p->step_end <= p->U),
+                "las_decoder_persist_fwd: greedy: window [step_begin, step_end) = [%d, %d) outside [0, U = %d]", p->step_begin, p->step_end, p->U);
+    LAS_REQUIRE(!p->emb || (two && p->T0 > 0 && p->T0 <= p->K_in && p->ld_emb >= p->T0), "las_decoder_persist_fwd: greedy: emb needs the second cell and T0 columns");
+    pw = *p;
+    if (whole) pw.step_end = pw.U;
+    p = &pw;                         // (the kernels take the struct by value)
+  }
   hipStream_t st = (hipStream_t)stream;
   const int groups = (s->B + 7) / 8;
   // flags and granules start from zero; the 64-byte status header is sticky (cleared by the host after it has read it)
@@ -4263,7 +4451,10 @@ extern "C" int las_decoder_persist_fwd(const las_dec_persist* p, void* stream) {
     }                                                                                                                           \
     hipLaunchKernelGGL((dec_persist_fwd_kernel<__VA_ARGS__>), grid, dim3(256), lds_al, st, *p);                                 \
   } while (0)
-    if (two && p->sampling_prob > 0.f) {
+    if (two && greedy) {
+      if (res) LAS_AL_LAUNCH(P_SAMPLE_GREEDY, true, 2, 12, 12, false, 10, true);
+      else LAS_AL_LAUNCH(P_SAMPLE_GREEDY, false, 2, 12, 12, false, 10, true);
+    } else if (two && p->sampling_prob > 0.f) {
       if (res) LAS_AL_LAUNCH(true, true, 2, 12, 12, false, 10, true);
       else LAS_AL_LAUNCH(true, false, 2, 12, 12, false, 10, true);
     } else if (two) {
@@ -4294,7 +4485,15 @@ extern "C" int las_decoder_persist_fwd(const las_dec_persist* p, void* stream) {
     hipLaunchKernelGGL((dec_persist_fwd_lean_kernel<__VA_ARGS__>), grid, dim3(256), lbytes, st, *p);                            \
   } while (0)
     // 4 Hd / 32 columns per member = one, two or four 16-column tiles; 512 units: 8 of the 20 K chunks per wave resident
-    if (p->sampling_prob > 0.f) {           // (scheduled sampling inside the launch: decoder_units <= 256)
+    if (greedy) {                           // (free-running greedy decoding: decoder_units <= 256)
+      if (s->attention == LAS_ATT_LUONG) {
+        if (s->Hd == 256) LAS_LEAN_LAUNCH(LAS_ATT_LUONG, 2, 12, 12, P_SAMPLE_GREEDY);
+        else LAS_LEAN_LAUNCH(LAS_ATT_LUONG, 1, 12, 12, P_SAMPLE_GREEDY);
+      } else {
+        if (s->Hd == 256) LAS_LEAN_LAUNCH(LAS_ATT_BAHDANAU, 2, 12, 12, P_SAMPLE_GREEDY);
+        else LAS_LEAN_LAUNCH(LAS_ATT_BAHDANAU, 1, 12, 12, P_SAMPLE_GREEDY);
+      }
+    } else if (p->sampling_prob > 0.f) {    // (scheduled sampling inside the launch: decoder_units <= 256)
       if (s->attention == LAS_ATT_LUONG) {
         if (s->Hd == 256) LAS_LEAN_LAUNCH(LAS_ATT_LUONG, 2, 12, 12, true);
         else LAS_LEAN_LAUNCH(LAS_ATT_LUONG, 1, 12, 12, true);
@@ -4338,12 +4537,15 @@ extern "C" int las_decoder_persist_fwd(const las_dec_persist* p, void* stream) {
     if (!attr_set) {
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dec_persist_fwd_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dec_persist_fwd_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dec_persist_fwd_kernel<P_SAMPLE_GREEDY, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       attr_set = true;
     }
-    if (p->sampling_prob > 0.f) hipLaunchKernelGGL((dec_persist_fwd_kernel<true, true>), grid, dim3(256), lds, st, *p);
+    if (greedy) hipLaunchKernelGGL((dec_persist_fwd_kernel<P_SAMPLE_GREEDY, true>), grid, dim3(256), lds, st, *p);
+    else if (p->sampling_prob > 0.f) hipLaunchKernelGGL((dec_persist_fwd_kernel<true, true>), grid, dim3(256), lds, st, *p);
     else hipLaunchKernelGGL((dec_persist_fwd_kernel<false, true>), grid, dim3(256), lds, st, *p);
   } else {
-    if (p->sampling_prob > 0.f) hipLaunchKernelGGL((dec_persist_fwd_kernel<true, false>), grid, dim3(256), lds, st, *p);
+    if (greedy) hipLaunchKernelGGL((dec_persist_fwd_kernel<P_SAMPLE_GREEDY, false>), grid, dim3(256), lds, st, *p);
+    else if (p->sampling_prob > 0.f) hipLaunchKernelGGL((dec_persist_fwd_kernel<true, false>), grid, dim3(256), lds, st, *p);
     else hipLaunchKernelGGL((dec_persist_fwd_kernel<false, false>), grid, dim3(256), lds, st, *p);
   }
   LAS_LAUNCH_CHECK("persistent decoder fwd launch");

@@ -113,6 +113,7 @@ _SIGS = {
     'las_decoder_persist_supported': ([C.c_int] * 5, C.c_int),
     'las_decoder_persist_al_supported': ([_i32, _i32, _i32, _i32, _i32, _i32], C.c_int),
     'las_decoder_persist2_supported': ([_i32, _i32, _i32, _i32, _i32, _i32], C.c_int),
+    'las_decoder_persist_greedy_supported': ([_i32] * 9, C.c_int),
     'las_decoder_persist_workspace_bytes': ([C.c_int, C.c_int, C.c_int, C.c_int], C.c_size_t),
     'las_decoder_persist_max_batch': ([], C.c_int),
     'las_decoder_persist_fwd': ([_vp, _vp], C.c_int),
@@ -164,7 +165,9 @@ class DecPersist(C.Structure):
         ('walT', _vp), ('ld_wal', _i64), ('A', _i32), ('x_att_off', _i32), ('att_out', _vp), ('ld_att', _i64), ('inc_p', _i64),
         ('k1T', _vp), ('ldk1', _i64), ('K1_in', _i32), ('wiring', _i32), ('bias1', _vp), ('c1', _vp), ('gates1', _vp), ('h1', _vp),
         ('win0', _i32), ('win1', _i32), ('in_stream0', C.c_uint32), ('in_stream1', C.c_uint32),
-        ('emb', _vp), ('ld_emb', _i64), ('T0', _i32), ('reserved_t0', _i32)]
+        ('emb', _vp), ('ld_emb', _i64), ('T0', _i32), ('reserved_t0', _i32),
+        ('greedy', _i32), ('eos_id', _i32), ('sample_ids', _vp), ('ld_samples', _i64), ('finished', _vp), ('final_len', _vp),
+        ('unfinished', _vp), ('step_begin', _i32), ('step_end', _i32)]
 
 
 class DecStepBwd(C.Structure):

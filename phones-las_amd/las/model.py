@@ -589,6 +589,10 @@ class Speller:
         keys = self._keys(memory, B, Tm)
         W = M + Hd
         S = max_iterations
+        self.last_decode_route, self.last_decode_launches = 'steps', 0
+        if greedy_persist_enabled(B, S) and lib.las_decoder_persist_greedy_supported(
+                Hd, M, W, 0, self.att, hip.NORM_SOFTMAX, 0, 0, Vp) == 1:
+            return self._forward_greedy_persist(memory, mem_len, keys, c0, h0, S)
         ah = torch.zeros(2, B, W, dtype=bf, device=dev)
         ah[0, :, M:].copy_(h0)
         cs = torch.empty(2, B, Hd, dtype=f32, device=dev)
@@ -625,6 +629,90 @@ class Speller:
             if bool(finished.all()):
                 break
         return logits[:, :steps, :V], samples[:, :steps], final_len, align[:, :steps]
+
+    def _forward_greedy_persist(self, memory, mem_len, keys, c0, h0, S):
+        """forward_greedy's loop as windows of one persistent launch each (las_dec_persist with `greedy`): the launch forms
+        the logits, takes the argmax, feeds it and keeps the finished / length words; the host reads ONE word per window.
+        Buffers as in forward_train's one-launch route, with capacity S = max_iterations."""
+        d = self.hp
+        B, Tm, M = memory.shape
+        Hd, V, Vp, W, U = self.Hd, self.V, self.Vp, M + self.Hd, S
+        dev, bf, f32, i32 = memory.device, torch.bfloat16, torch.float32, torch.int32
+        lib = hip.lib()
+        AH = torch.empty(B, U, W, dtype=bf, device=dev)
+        cs = torch.empty(B, U + 1, Hd, dtype=f32, device=dev)
+        AH[:, 0, :M].zero_()                  # attention_{-1} = 0
+        AH[:, 0, M:].copy_(h0)
+        cs[:, 0].copy_(c0)
+        gates = torch.empty(B, 4 * Hd, dtype=f32, device=dev)      # (nothing reads the gates of a decode: one row, step increment 0)
+        h_all = torch.empty(B, U, Hd, dtype=bf, device=dev)
+        align = torch.zeros(B, U, Tm, dtype=f32, device=dev)
+        ctx_all = torch.empty(B, U, M, dtype=bf, device=dev)
+        fed = torch.full((B, U), d.eos_id, dtype=i32, device=dev)
+        fed[:, 0] = d.sos_id
+        p = hip.DecPersist()
+        p.s = self._step_struct(
+            B, Tm, 0, hip.addr(fed), U, hip.addr(cs), (U + 1) * Hd, hip.addr(gates), 4 * Hd,
+            hip.addr(cs, Hd), (U + 1) * Hd, hip.addr(h_all), U * Hd, hip.addr(AH, W + M) if U > 1 else 0, U * W,
+            keys, memory, mem_len, hip.addr(align), 0, U * Tm, 0, Hd, hip.addr(ctx_all), U * M,
+            hip.addr(AH, W) if U > 1 else 0, U * W)
+        p.U, p.K_in = U, W
+        p.inc_tok, p.inc_cprev, p.inc_gates, p.inc_cout, p.inc_h, p.inc_h2 = 1, Hd, 0, Hd, Hd, W
+        p.inc_align, p.inc_pq, p.inc_ctx, p.inc_ctx2 = Tm, Hd, M, W
+        p.x, p.ldx, p.inc_x = hip.addr(AH), U * W, W
+        p.kT, p.ldk = hip.addr(self.kcT), W
+        p.wprojT, p.ldw, p.bproj = hip.addr(self.wprojT), M, hip.addr(self.bproj)
+        ws = self._persist_workspace('fwd', lib.las_decoder_persist_workspace_bytes(B, Tm, Hd, M))
+        p.workspace = hip.addr(ws)
+        self._persist_ws = ws
+        flops = 2.0 * B * (W * 4 * Hd + Tm * Hd + Tm * M + M * Vp)
+        logits, samples, final_len, steps, self.last_decode_launches = run_greedy_windows(p, B, U, V, Vp, d.eos_id, dev, flops)
+        self.last_decode_route = 'persist'
+        self.last_decode_buffers = {'ctx': ctx_all[:, :steps], 'h': h_all[:, :steps]}      # (what the tests replay against)
+        return logits[:, :steps, :V], samples[:, :steps], final_len, align[:, :steps]
+
+
+def greedy_persist_enabled(B, max_iterations):
+    """The one-launch greedy route is on unless LAS_DEC_PERSIST_GREEDY=0 or LAS_DEC_PERSIST=0 (read at every call); the
+    batch must fit one launch (co-residency) and there must be a step to run."""
+    return (os.environ.get('LAS_DEC_PERSIST', '1') != '0' and os.environ.get('LAS_DEC_PERSIST_GREEDY', '1') != '0'
+            and max_iterations >= 1 and B <= 4 * hip.lib().las_decoder_persist_max_batch())
+
+
+GREEDY_WINDOW = 32      # steps per launch of the one-launch greedy decode (LAS_DEC_GREEDY_WINDOW overrides)
+
+
+def run_greedy_windows(p, B, U, V, Vp, eos_id, dev, flops_per_step):
+    """The window protocol of the one-launch greedy decode, shared by both spellers.  `p` (hip.DecPersist) describes the
+    whole capacity U; this adds the greedy fields and launches [0, w), [w, 2w), ... until every utterance has emitted
+    </s> (one word read per window: the count of unfinished utterances the launch maintains) or U steps are done.
+    Returns (logits [B,U,Vp], sample_ids [B,U], final_len [B], steps, launches): rows past `steps` are not meaningful."""
+    f32, i32 = torch.float32, torch.int32
+    lib, st = hip.lib(), hip.stream()
+    w = int(os.environ.get('LAS_DEC_GREEDY_WINDOW', '0') or 0)
+    w = max(1, min(w if w > 0 else GREEDY_WINDOW, U))
+    logits = torch.empty(B, U, Vp, dtype=f32, device=dev)
+    samples = torch.full((B, U), eos_id, dtype=i32, device=dev)
+    state = torch.zeros(2 * B + 1, dtype=i32, device=dev)         # finished [B] | final_len [B] | unfinished
+    state[2 * B] = B
+    plog = torch.empty(w, B, 4, Vp, dtype=f32, device=dev)
+    p.greedy, p.eos_id = 1, eos_id
+    p.logits, p.ld_logits, p.plog, p.V, p.Vp = hip.addr(logits), U * Vp, hip.addr(plog), V, Vp
+    p.sample_ids, p.ld_samples = hip.addr(samples), U
+    p.finished, p.final_len, p.unfinished = hip.addr(state), hip.addr(state, B), hip.addr(state, 2 * B)
+    launches, t0, done = 0, 0, False
+    while t0 < U and not done:
+        t1 = min(t0 + w, U)
+        p.step_begin, p.step_end = t0, t1
+        tok = hip.prof_begin('dec_persist_greedy', flops_per_step * (t1 - t0))
+        hip.check(lib.las_decoder_persist_fwd(C.byref(p), st))
+        hip.prof_end(tok)
+        launches += 1
+        done = int(state[2 * B].item()) == 0                      # the one synchronisation of the window
+        t0 = t1
+    final_len = state[B:2 * B]
+    steps = int(final_len.max().item()) if done else U
+    return logits, samples, final_len.clone(), steps, launches
 
 
 BasicDecoderOutput = None

@@ -1008,6 +1008,96 @@ class GeneralSpeller:
         return dmem, d_state
 
     # ------------------------------------------------------------------------------------------------------------------
+    def _greedy_persist_ok(self, B, S):
+        """Two decoder cells, softmax attentions, no attention layer: the greedy decode as windows of one persistent launch
+        (las_dec_persist with `greedy`).  LAS_DEC_PERSIST_GREEDY=0 / LAS_DEC_PERSIST=0 / LAS_DEC_PERSIST2=0: step by step."""
+        import os
+        from .model import greedy_persist_enabled
+        if not greedy_persist_enabled(B, S) or os.environ.get('LAS_DEC_PERSIST2', '1') == '0':
+            return False
+        if self.NL != 2 or self.sigmoid or self.has_al or self.mono or self.custom or self.binf is not None:
+            return False
+        Kp = (self.win[0] + self.Hd + 63) // 64 * 64
+        return hip.lib().las_decoder_persist_greedy_supported(self.Hd, self.M, Kp, self.win[1] + self.Hd, self.att, self._norm(False),
+                                                              1 if self.bottom else 0, 0, self.Vop) == 1
+
+    def _forward_greedy_persist(self, memory, mem_len, init, S):
+        """forward_greedy's loop for two cells as windows of one persistent launch each: the operands of
+        _forward_train_persist(two=True) with capacity U = S, fed[:, 0] = <s> and everything behind it produced by the launch."""
+        from .model import run_greedy_windows
+        d = self.hp
+        B, Tm, M = memory.shape
+        Hd, V, Vp, U = self.Hd, self.V, self.Vop, S
+        dev, bf, f32 = memory.device, torch.bfloat16, torch.float32
+        lib = hip.lib()
+        keys = self._keys(memory)
+        Tmp = _r8(Tm)
+        W0 = self.win[0] + Hd
+        Kp = (W0 + 63) // 64 * 64
+        T0 = self.T0
+        feed = T0 + M                                          # column of h0 in cell 0's operand row
+        Xp = torch.zeros(B, U, Kp, dtype=bf, device=dev)
+        Xp[:, 0, feed:feed + Hd].copy_(init[0][1])
+        if getattr(self, '_kTp', None) is None or self._kTp.shape[1] != Kp:
+            self._kTp = torch.zeros(4 * Hd, Kp, dtype=bf, device=dev)
+        self._kTp[:, :W0].copy_(self.kT[0])
+        fed = torch.full((B, U), d.eos_id, dtype=torch.int32, device=dev)
+        fed[:, 0] = d.sos_id
+        cs0 = torch.empty(B, U + 1, Hd, dtype=f32, device=dev)
+        cs0[:, 0].copy_(init[0][0])
+        gates0 = torch.empty(B, 4 * Hd, dtype=f32, device=dev)      # (nothing reads the gates of a decode: one row, step increment 0)
+        gates1 = torch.empty(B, U, 4 * Hd, dtype=f32, device=dev)
+        h0_all = torch.empty(B, U, Hd, dtype=bf, device=dev)
+        align = torch.zeros(B, U, Tmp, dtype=f32, device=dev)
+        ctx = torch.empty(B, U, M, dtype=bf, device=dev)
+        p = hip.DecPersist()
+        s = p.s
+        s.B, s.Hd, s.M, s.Tm, s.attention, s.mode = B, Hd, M, Tm, self.att, 0
+        s.tok_rows, s.tok_ids, s.tok_stride = (0 if T0 else hip.addr(self.tok)), hip.addr(fed), U
+        s.bias = hip.addr(self.bias[0])
+        s.c_prev, s.ldcp = hip.addr(cs0), (U + 1) * Hd
+        s.gates_out, s.ldg = hip.addr(gates0), 4 * Hd
+        s.c_out, s.ldco = hip.addr(cs0, Hd), (U + 1) * Hd
+        s.h_out, s.ldh = hip.addr(h0_all), U * Hd
+        s.h_out2, s.ldh2 = (hip.addr(Xp, Kp + feed) if U > 1 else 0), U * Kp
+        s.keys, s.values, s.mem_len = hip.addr(keys), hip.addr(memory), hip.addr(mem_len)
+        if self.uses_wq:
+            s.wq = hip.addr(self.wq)
+        if self.additive:
+            s.att_v = hip.addr(self.att_v)
+        s.align_out, s.lda = hip.addr(align), U * Tmp
+        s.ctx_out, s.ldc = hip.addr(ctx), U * M
+        s.ctx_out2, s.ldc2 = (hip.addr(Xp, Kp + T0) if U > 1 else 0), U * Kp
+        s.drop_keep, s.feed_width = 1.0, self.E + self.A
+        if T0:                                                 # dense token feed: <s> embedded into the first row, the rest by the launch
+            Xp[:, 0, :self.Ep].copy_(self.emb_bf[d.sos_id])
+            s.feed_width = self.win[0]
+            p.emb, p.ld_emb, p.T0 = hip.addr(self.emb_bf), self.Ep, T0
+        s.norm = hip.NORM_SOFTMAX
+        p.U, p.K_in = U, Kp
+        if self.uses_wq and self.wq_pkT is not None and Hd in (128, 256):
+            p.wq_packed = hip.addr(self.wq_pkT)
+        p.inc_tok, p.inc_cprev, p.inc_gates, p.inc_cout, p.inc_h, p.inc_h2 = 1, Hd, 0, Hd, Hd, Kp
+        p.inc_align, p.inc_pq, p.inc_ctx, p.inc_ctx2, p.inc_p = Tmp, Hd, M, Kp, Tmp
+        p.x, p.ldx, p.inc_x = hip.addr(Xp), U * Kp, Kp
+        p.kT, p.ldk = hip.addr(self._kTp), Kp
+        K1 = self.win[1] + Hd
+        c1 = torch.empty(B, U + 1, Hd, dtype=f32, device=dev)
+        h1 = torch.empty(B, U + 1, Hd, dtype=bf, device=dev)
+        hip.fill_many(copy=[(c1[:, 0], init[1][0].float()), (h1[:, 0], init[1][1].float())])
+        p.k1T, p.ldk1, p.K1_in, p.wiring = hip.addr(self.kT[1]), K1, K1, 1 if self.bottom else 0
+        p.bias1, p.c1, p.gates1, p.h1 = hip.addr(self.bias[1]), hip.addr(c1), hip.addr(gates1), hip.addr(h1)
+        p.wprojT, p.ldw, p.bproj = hip.addr(self.wprojT), self.P, hip.addr(self.bproj)
+        ws = self._persist_workspace('fwd', lib.las_decoder_persist_workspace_bytes(B, Tm, Hd, M))
+        p.workspace = hip.addr(ws)
+        self._persist_ws = ws
+        flops = 2.0 * B * (Kp * 4 * Hd + K1 * 4 * Hd + Tm * Hd + Tm * M + self.P * Vp)
+        logits, samples, final_len, steps, self.last_decode_launches = run_greedy_windows(p, B, U, V, Vp, d.eos_id, dev, flops)
+        self.last_decode_route = 'persist'
+        self.last_decode_buffers = {'ctx': ctx[:, :steps], 'h': h0_all[:, :steps]}          # (what the tests replay against)
+        self.last_raw_outputs = (h1[:, 1:] if self.bottom else ctx)[:, :steps]
+        return logits[:, :steps, :V], samples[:, :steps], final_len, align[:, :steps, :Tm]
+
     def forward_beam(self, memory, mem_len, encoder_state, max_iterations, beam_width, partial_targets=None):
         """BeamSearchDecoder decode (las/model.py:219-226,298-319,346-347): the batch tiled beam_width times, one
         las_beam_step per decoder step, decoder state gathered by the parent beams, gather_tree at the end.
@@ -1051,6 +1141,9 @@ class GeneralSpeller:
             L = int(prefix.shape[1])
         S = max_iterations + L
         init, _ = self._init_states(encoder_state, B)
+        self.last_decode_route, self.last_decode_launches = 'steps', 0
+        if K <= 0 and not binary and self._greedy_persist_ok(B, S):
+            return self._forward_greedy_persist(memory, mem_len, init, S)
         ids0 = torch.full((B, 1), d.sos_id, dtype=torch.int32, device=dev)
         fed = torch.full((B, max(S, 1)), d.eos_id, dtype=torch.int32, device=dev)
         fed[:, :1] = ids0
