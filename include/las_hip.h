@@ -938,6 +938,37 @@ int las_frame_binf_count(const uint8_t* P, const int64_t* p_off, const int32_t* 
                          const int32_t* att_ld, const int32_t* n_frames, int n_utt, int32_t* seg_phone, int32_t* counts,
                          void* stream);
 
+/* Evaluation metrics (utils/metrics_utils.py:8-41 and model_helper.py:347-367 of the reference; csrc/metrics.hip), added under
+ * version 105.  All results are integers and exact.
+ * las_edit_distance_batch: n_pairs (hypothesis, reference) pairs of two ragged int32 batches, read in place, in one launch.
+ * Sequence i of a side starts at element off[i] (device int64) of its buffer of `size` elements and has len[i] (device int32)
+ * elements.  Pair i takes hypothesis i and reference ref_of_hyp[i] < n_refs (device int32; NULL: reference i, n_refs = n_pairs),
+ * so the K beams of one utterance share a reference.  mapping (device int32, n_map entries; NULL with n_map = 0: none) replaces
+ * every id x by mapping[x] on both sides, whatever the flags.  flags bit 0 set: dense_to_sparse(merge_repeated=True) on both
+ * sides, after the mapping: append eos_id, then keep element i iff mapped[i] != mapped[i + 1] and i is before the first mapped
+ * value equal to eos_id and mapped[i] != -1 (the last element of every run is kept; -1 takes part in the run comparison before
+ * it is dropped).  Bit 0 clear: the (mapped) sequences as given.  Outputs per pair (int32): dist = the unit-cost Levenshtein
+ * distance of the kept tokens, hyp_n / ref_n = their numbers; the normalised distance is dist / ref_n, formed by the caller.
+ * dist = -1 (hyp_n = ref_n = 0): a length outside [0, len_max], a reference index outside [0, n_refs) or a sequence that leaves
+ * its buffer -- nothing of that pair is read; dist = -2: an id outside [0, n_map) under a mapping -- it is never used as an
+ * index.  The other pairs of the launch are scored all the same.  len_max bounds the raw lengths of the call (<= 8191); a
+ * workspace of las_edit_distance_workspace_bytes(len_max, n_pairs) bytes holds the tokens and the table row of pairs with a raw
+ * length above 1023, which do not fit in LDS (0 bytes: none needed, workspace may be NULL). */
+size_t las_edit_distance_workspace_bytes(int len_max, int n_pairs);
+int las_edit_distance_batch(const int32_t* hyp, int64_t hyp_size, const int64_t* hyp_off, const int32_t* hyp_len,
+                            const int32_t* ref, int64_t ref_size, const int64_t* ref_off, const int32_t* ref_len,
+                            const int32_t* ref_of_hyp, int n_pairs, int n_refs, const int32_t* mapping, int n_map, int eos_id,
+                            int flags, int len_max, int32_t* dist, int32_t* hyp_n, int32_t* ref_n, void* workspace,
+                            size_t workspace_bytes, void* stream);
+/* las_ctc_greedy_batch: tf.nn.ctc_greedy_decoder(merge_repeated=True) + tf.sparse.to_dense of fp32 logits [B, T, C] (frame
+ * stride ld >= C elements, utterance stride T * ld) in one launch, no host round trip.  Per frame t < logit_len[b] (clamped to
+ * [0, T]) the first-index argmax over c < C (tf.argmax); the class is emitted iff it differs from the previous frame's class
+ * (-1 before frame 0) and is not the blank, class C - 1.  decoded [B, T] int32: the emitted classes at the front of the row,
+ * zeros behind; dec_len[b] their number.  The logits are taken to be FINITE: the class of a frame that holds a
+ * NaN is unspecified (no comparison with a NaN is true), where tf.argmax returns the NaN's index. */
+int las_ctc_greedy_batch(const float* logits, int64_t ld, const int32_t* logit_len, int B, int T, int C, int32_t* decoded,
+                         int32_t* dec_len, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Input path (utils/dataset_utils.py:138-283 of the reference: tf.data.TFRecordDataset ->
  * tf.parse_single_sequence_example -> (x - mean) / std -> padded_batch).  Host functions; `data` is the image of a

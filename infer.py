@@ -101,7 +101,7 @@ def main(args):
             raise SystemExit('--calc_frame_binf_accuracy needs --mapping_for_frame_accuracy')
     from phones_las_amd import utils
     from phones_las_amd import model_helper as mh
-    from phones_las_amd.utils.metrics_utils import _levenshtein
+    from phones_las_amd.utils.metrics_utils import levenshtein_lists
     from train import load_checkpoint, to_device
 
     vocab_list = utils.load_vocab(args.vocab)
@@ -162,7 +162,10 @@ def main(args):
         targets = [[x.strip().lower() for x in cells[2].split()] for cells in _read_plain_targets(args.plain_targets)]
     else:
         targets = record_targets
-    err = tot = optimistic_err = 0
+    # Every symbol of hypotheses and targets becomes an integer through one dict (--plain_targets words outside the vocabulary
+    # included); all utterances x beams are then scored in ONE launch (csrc/metrics.hip), the sequences as they are.
+    sym_ids = {}
+    hyps, refs, ref_of_hyp, first_hyp = [], [], [], []
     for k, (beams, t) in enumerate(zip(beams_all, targets)):      # zip: the shorter of the two, as the reference's loop (infer.py:276)
         texts = [text_of(i) for i in beams]
         if args.plain_targets and text_mapping is not None:
@@ -170,9 +173,15 @@ def main(args):
             t = [vocab_list[text_mapping[vocab_list_orig.index(x)]] for x in t]
         if frame_acc is not None:                       # infer.py:326-331, in utterance order
             frame_acc.report(k, t)
-        err += _levenshtein(texts[0], t)                # the best-scoring beam is the hypothesis (infer.py:286-288)
-        optimistic_err += min(_levenshtein(x, t) for x in texts)
-        tot += len(t)
+        first_hyp.append(len(hyps))
+        hyps += [[sym_ids.setdefault(x, len(sym_ids)) for x in text] for text in texts]
+        ref_of_hyp += [k] * len(texts)
+        refs.append([sym_ids.setdefault(x, len(sym_ids)) for x in t])
+    dist = levenshtein_lists(hyps, refs, ref_of_hyp, dev)
+    first_hyp.append(len(hyps))
+    err = sum(dist[i] for i in first_hyp[:-1])          # the best-scoring beam is the hypothesis (infer.py:286-288)
+    optimistic_err = sum(min(dist[i:j]) for i, j in zip(first_hyp, first_hyp[1:]))
+    tot = sum(len(t) for t in refs)
     with open(os.path.join(args.model_dir, 'infer_targets.txt'), 'w') as f:
         f.write('\n'.join(args.delimiter.join(t) for t in targets))
     predictions = [{'transcription': args.delimiter.join(text_of(beams[0]))} for beams in beams_all]      # infer.py:345-353

@@ -34,6 +34,8 @@ extern "C" int las_set_knob(const char* name, int value) {
   return LAS_OK;
 }
 
+// 105 (still): las_edit_distance_batch / las_edit_distance_workspace_bytes / las_ctc_greedy_batch (csrc/metrics.hip,
+// utils/metrics_utils.py) were added under 105, nothing else changed;
 // 104: las_attention_dtw_batch / las_attention_dtw_workspace_bytes / las_frame_binf_count (csrc/align.hip, frame_binf.py) added,
 // nothing else changed;
 // 103: las_resample_batch (csrc/resample.hip: resampy 0.2.2 kaiser_best over a ragged batch, audio.py) added, nothing else changed;

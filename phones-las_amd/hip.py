@@ -106,6 +106,9 @@ _SIGS = {
     'las_attention_dtw_workspace_bytes': ([_i32, _i32, _i32], C.c_size_t),
     'las_attention_dtw_batch': ([_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp], C.c_int),
     'las_frame_binf_count': ([_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp], C.c_int),
+    'las_edit_distance_workspace_bytes': ([_i32, _i32], C.c_size_t),
+    'las_edit_distance_batch': ([_vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, C.c_size_t, _vp], C.c_int),
+    'las_ctc_greedy_batch': ([_vp, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp], C.c_int),
     'las_add_masked': ([_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _f32, C.c_uint32, C.c_uint32, C.c_uint64, _i64, _vp], C.c_int),
     'las_add_noise': ([_vp, _i64, _f32, C.c_uint32, C.c_uint32, _vp], C.c_int),
     'las_gemm_tn_lstm_workspace_bytes': ([C.c_int, C.c_int, C.c_int], C.c_size_t),
@@ -601,3 +604,80 @@ def colsum_bf16(X, M, N, out, ldx=None, perm_h=0):
             raise LasError('colsum_bf16: new workspace during graph capture (run the step once eagerly first)')
         ws = _CS_WS[key] = torch.zeros(max(need, 1 << 18), dtype=torch.uint8, device='cuda')
     check(lib().las_colsum_bf16_ws(p(X), ldx, M, N, p(out), perm_h, p(ws), ws.numel(), stream()))
+
+
+# ---------------------------------------------------------------------------------------------
+# evaluation metrics (csrc/metrics.hip)
+# ---------------------------------------------------------------------------------------------
+ED_MERGE = 1              # las_edit_distance_batch flag bit 0: the reference's dense_to_sparse(merge_repeated=True)
+ED_LEN_MAX = 8191
+_ED_WS = {}
+
+
+def edit_distance_batch(hyp, hyp_off, hyp_len, ref, ref_off, ref_len, eos_id, len_max, ref_of_hyp=None, mapping=None,
+                        flags=ED_MERGE):
+    """las_edit_distance_batch: (dist, hyp_n, ref_n), int32 device tensors of one entry per hypothesis.  hyp / ref: int32 device
+    buffers; *_off int64 and *_len int32 device tensors, one entry per sequence; ref_of_hyp int32 (None: pair i takes reference
+    i); mapping an int32 device tensor or None.  No synchronisation: status values (dist < 0) are the caller's to read,
+    edit_distance_status() raises on them."""
+    for t, dt, name in ((hyp, torch.int32, 'hyp'), (hyp_off, torch.int64, 'hyp_off'), (hyp_len, torch.int32, 'hyp_len'),
+                        (ref, torch.int32, 'ref'), (ref_off, torch.int64, 'ref_off'), (ref_len, torch.int32, 'ref_len'),
+                        (ref_of_hyp, torch.int32, 'ref_of_hyp'), (mapping, torch.int32, 'mapping')):
+        if t is not None:
+            if not t.is_cuda:
+                raise LasError('expected a CUDA tensor; the LAS ops have no CPU path')
+            _req(t, dt, name)
+    n_pairs, n_refs = hyp_off.numel(), ref_off.numel()
+    if hyp_len.numel() != n_pairs or ref_len.numel() != n_refs or (ref_of_hyp is not None and ref_of_hyp.numel() != n_pairs):
+        raise LasError('edit_distance_batch: offsets, lengths and ref_of_hyp disagree in size')
+    dev = hyp.device
+    out = torch.empty(3, max(n_pairs, 1), dtype=torch.int32, device=dev)
+    if n_pairs == 0:
+        return out[0, :0], out[1, :0], out[2, :0]
+    need = lib().las_edit_distance_workspace_bytes(int(len_max), n_pairs)
+    ws = None
+    if need:
+        key = (torch.cuda.current_device(), _ws_lane)
+        ws = _ED_WS.get(key)
+        if ws is None or ws.numel() < need:
+            ws = _ED_WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+    check(lib().las_edit_distance_batch(p(hyp), hyp.numel(), p(hyp_off), p(hyp_len), p(ref), ref.numel(), p(ref_off), p(ref_len),
+                                        p(ref_of_hyp), n_pairs, n_refs, p(mapping), mapping.numel() if mapping is not None else 0,
+                                        int(eos_id), int(flags), int(len_max), p(out[0]), p(out[1]), p(out[2]), p(ws),
+                                        ws.numel() if ws is not None else 0, stream()))
+    return out[0], out[1], out[2]
+
+
+def edit_distance_status(dist):
+    """Raises on the status values of las_edit_distance_batch in `dist` (a host sequence or a tensor; a device tensor is copied,
+    which synchronises): -1 -> ValueError, -2 -> IndexError."""
+    d = dist.tolist() if hasattr(dist, 'tolist') else list(dist)
+    for i, v in enumerate(d):
+        if v == -1:
+            raise ValueError('edit distance: pair %d has a length above len_max or lies outside its buffer' % i)
+        if v == -2:
+            raise IndexError('edit distance: pair %d holds an id outside the mapping' % i)
+
+
+def ctc_greedy_batch(logits, logit_len, C=None):
+    """las_ctc_greedy_batch on fp32 logits [B, T, >= C] (unit inner stride, frame stride logits.stride(1), utterances back to
+    back): (decoded [B, T] int32, zero-filled behind the decoded ids; dec_len [B] int32).  Blank = class C - 1."""
+    if not (logits.is_cuda and logit_len.is_cuda):
+        raise LasError('expected a CUDA tensor; the LAS ops have no CPU path')
+    if logits.dtype != torch.float32 or logits.dim() != 3:
+        raise LasError('ctc_greedy_batch: logits must be float32 [B, T, C], got %s %s' % (logits.dtype, tuple(logits.shape)))
+    B, T, W = logits.shape
+    C = W if C is None else int(C)
+    ld = logits.stride(1)
+    if logits.stride(2) != 1 or logits.stride(0) != T * ld or not 0 < C <= W:
+        raise LasError('ctc_greedy_batch: logits must be [B, T, >= C] with unit inner stride and utterances back to back')
+    _req(logit_len, torch.int32, 'logit_len')
+    if logit_len.numel() != B:
+        raise LasError('ctc_greedy_batch: %d lengths for %d utterances' % (logit_len.numel(), B))
+    decoded = torch.empty(B, T, dtype=torch.int32, device=logits.device)
+    dec_len = torch.empty(B, dtype=torch.int32, device=logits.device)
+    if B and T:
+        check(lib().las_ctc_greedy_batch(p(logits), ld, p(logit_len), B, T, C, p(decoded), p(dec_len), stream()))
+    else:
+        dec_len.zero_()
+    return decoded, dec_len

@@ -500,27 +500,19 @@ class CtcHead:
                                    hip.p(loss_out), hip.p(self.per_example), hip.p(self.dlogits), hip.stream()))
         self.memory = memory
 
+    def logits_only(self, memory):
+        """The head's logits [B, Tm, Cp] fp32 (classes [0, C); the columns behind are padding) without the loss: the operand
+        of the EVAL metric `ctc_edit_distance`."""
+        B, Tm, M = memory.shape
+        logits = torch.empty(B, Tm, self.Cp, dtype=torch.float32, device=memory.device)
+        hip.gemm_nt(memory, self.wT, logits, B * Tm, self.Cp, M, lda=M, ldb=M, ldc=self.Cp, bias=self.bias)
+        return logits
+
     def backward(self, dmem, grads):
         B, Tm, M = self.memory.shape
         hip.gemm_nt(self.dlogits, self.wn, dmem, B * Tm, M, self.Cp, lda=self.Cp, ldb=self.Cp, ldc=M, accumulate=True)
         hip.gemm_tn(self.memory, self.dlogits, grads[self.K], M, self.C, B * Tm, lda=M, ldb=self.Cp, ldc=self.C, split_k=4)
         hip.colsum_bf16(self.dlogits, B * Tm, self.C, grads[self.Bn], ldx=self.Cp)
-
-
-def ctc_greedy_decode(logits, logit_len):
-    """tf.nn.ctc_greedy_decoder (model_helper.py:351-353): blank = LAST class, merge repeated; host-side metric."""
-    best = logits.argmax(-1).cpu().tolist()
-    C = logits.shape[-1]
-    out = []
-    for b, row in enumerate(best):
-        prev, seq = -1, []
-        for t in range(int(logit_len[b])):
-            k = row[t]
-            if k != prev and k != C - 1:
-                seq.append(k)
-            prev = k
-        out.append(seq)
-    return out
 
 
 class LasModel:
@@ -979,10 +971,14 @@ class LasModel:
         if logits is None:
             return None
         width = getattr(self.speller, 'Vo', self.speller.V)
-        ids = logits[..., :width].argmax(-1).to(torch.int32).cpu().numpy()
+        ids = logits[..., :width].argmax(-1).to(torch.int32)
         tout = labels['targets_outputs']
+        eos, mapping = self.params.decoder.eos_id, self.params.mapping
+        if torch.is_tensor(tout) and tout.is_cuda and not metrics_utils.host_metrics_forced():
+            return float(np.mean(metrics_utils.edit_distance_on_device(ids, tout[:, :ids.shape[1]], eos, mapping)))
+        ids = ids.cpu().numpy()
         tout = (tout.cpu().numpy() if torch.is_tensor(tout) else np.asarray(tout))[:, :ids.shape[1]]
-        return float(np.mean(metrics_utils.edit_distance(ids, tout, self.params.decoder.eos_id, self.params.mapping)))
+        return float(np.mean(metrics_utils.edit_distance(ids, tout, eos, mapping)))
 
     # -- inference ------------------------------------------------------------------------------
     def predict(self, features, transparent_projection=False):
@@ -1033,6 +1029,7 @@ class LasModel:
             return out
         primary = None
         out['_decoders'] = []                # (kind, logits, final_sequence_length) per decoder, for evaluate()
+        out['_memory'] = (mem, mem_len)      # the encoder outputs and their lengths, for evaluate()'s CTC metric
         for mod, kind in self.spellers:
             logits, ids, final_len, align = mod.forward_greedy(mem, mem_len, state, max_it)
             out['_decoders'].append((kind, logits, final_len))
@@ -1068,7 +1065,15 @@ class LasModel:
 
     def evaluate(self, features, labels):
         """EVAL branch: free-running greedy decode, the padded losses of every decoder (model_helper.py:54-76,98-130,
-        319-342) and the edit distance of the first decoder's phone ids (:299-309)."""
+        319-342) and the edit distance of the first decoder's phone ids (:299-309), scored on the device
+        (metrics_utils.edit_distance_on_device: one launch, B integer triples copied back; LAS_HOST_METRICS=1 takes the host
+        path, with the same floats).
+        A model with a CTC head (--ctc_weight > 0) adds, as model_helper.py:347-367 does, pred['ctc_decoded'] [B, D] int32 (the
+        greedy CTC decode of the head's logits, dense, D = the batch's longest decode), pred['ctc_decoded_length'] [B] and
+        pred['ctc_edit_distance'] = edit_distance(ctc_decoded, targets_outputs, eos_id, mapping), a list of floats.  The
+        reference's quirk is kept: sparse.to_dense pads the shorter rows with id 0, and the metric's run rule keeps that padding
+        as ONE extra <unk> (id 0) token -- unless the row's last decoded id is 0 (it merges) or the row is the batch's longest
+        (no padding).  The number therefore depends on what else is in the batch, as the reference's does."""
         pred = self.predict(features)
         tout, tlen = labels['targets_outputs'], labels['target_sequence_length']
         eos = self.params.decoder.eos_id
@@ -1083,7 +1088,16 @@ class LasModel:
             else:
                 l_, _ = compute_loss(logits.contiguous(), tout, final_len, tlen, EVAL, eos)
             loss = l_ if loss is None else loss + l_
-        ed = metrics_utils.edit_distance(pred['sample_ids'], tout, eos, self.params.mapping)
+        host = metrics_utils.host_metrics_forced()
+        score = metrics_utils.edit_distance if host else metrics_utils.edit_distance_on_device
+        ed = score(pred['sample_ids'], tout, eos, self.params.mapping)
+        if self.ctc is not None:
+            mem, mem_len = pred['_memory']
+            decoded, dec_len = hip.ctc_greedy_batch(self.ctc.logits_only(mem.contiguous()), mem_len.to(torch.int32).contiguous(),
+                                                    self.ctc.C)
+            decoded = decoded[:, :int(dec_len.max().item())]          # to_dense: as wide as the batch's longest decode
+            pred['ctc_decoded'], pred['ctc_decoded_length'] = decoded, dec_len
+            pred['ctc_edit_distance'] = score(decoded, tout, eos, self.params.mapping)
         return loss, ed, pred
 
     def check_device_status(self):
@@ -1149,8 +1163,10 @@ def las_model_fn(features, labels, mode, config, params, binf2phone=None, run_na
         return EstimatorSpec(mode, predictions=model.predict(features, transparent_projection=transparent_projection))
     if mode == EVAL:
         loss, ed, pred = model.evaluate(features, labels)
-        return EstimatorSpec(mode, loss=loss, predictions=pred,
-                             eval_metric_ops={'edit_distance': float(np.mean(ed))})
+        metrics = {'edit_distance': float(np.mean(ed))}
+        if 'ctc_edit_distance' in pred:
+            metrics['ctc_edit_distance'] = float(np.mean(pred['ctc_edit_distance']))
+        return EstimatorSpec(mode, loss=loss, predictions=pred, eval_metric_ops=metrics)
     model.vars.grad.zero_()
     audio_loss, logits, dlogits = model.forward_train(features, labels)
     loss = audio_loss + model.l2_loss()

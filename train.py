@@ -227,24 +227,26 @@ def evaluate(model, batches, dev, rank=0, world=1):
     replicas every batch is dealt round-robin to them (every replica walks the same batches) and the sums are
     all-reduced at the end, so all replicas leave the evaluation together."""
     from phones_las_amd import dp
-    loss_sum, n_batches, ed_sum, n_utt = 0.0, 0, 0.0, 0
+    loss_sum, n_batches, ed_sum, n_utt, ctc_sum = 0.0, 0, 0.0, 0, 0.0
     for i, (features, labels) in enumerate(batches):
         if world > 1 and i % world != rank:
             continue
         f, l = to_device(features, labels, dev)
-        loss, ed, _ = model.evaluate(f, l)
+        loss, ed, pred = model.evaluate(f, l)
         loss_sum += float(loss)
         n_batches += 1
         ed_sum += float(np.sum(ed))
         n_utt += len(ed)
+        ctc_sum += float(np.sum(pred.get('ctc_edit_distance', ())))       # CTC models: the head's own metric
     model.check_device_status()
     if world > 1:
-        loss_sum, n_batches, ed_sum, n_utt = dp.sum_floats([loss_sum, n_batches, ed_sum, n_utt])
+        loss_sum, n_batches, ed_sum, n_utt, ctc_sum = dp.sum_floats([loss_sum, n_batches, ed_sum, n_utt, ctc_sum])
     if not n_batches:
         return None, None
     res = (loss_sum / n_batches, ed_sum / max(n_utt, 1))
     if rank == 0:
-        print('eval: loss = %.5f, edit_distance = %.5f' % res)
+        print('eval: loss = %.5f, edit_distance = %.5f' % res
+              + (', ctc_edit_distance = %.5f' % (ctc_sum / max(n_utt, 1)) if model.ctc is not None else ''))
     return res
 
 
