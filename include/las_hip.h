@@ -759,6 +759,59 @@ int las_proj_ce(const las_bf16* ctx, int64_t ld_ctx, const las_bf16* wprojT, con
 int las_beam_step(const float* logits, int64_t ldl, float* log_probs, int32_t* finished, int32_t* lengths,
                   int32_t* word_ids, int32_t* parent_ids, int B, int K, int V, int eos, void* stream);
 
+/* The same step for any K * V, together with everything between the logits of step t and the operands of step t + 1, in ONE
+ * launch (csrc/beam.hip; one workgroup per utterance, no workgroup waits on another).  The log-softmax is las_beam_step's
+ * arithmetic and the selection is exact, so where las_beam_step runs the results are bit-identical; the K winners are merged
+ * out of each beam's own best min(K, V) candidates, which takes K * K words of LDS whatever V is.  K <= LAS_BEAM_MAX_WIDTH.
+ *   state      log_probs / finished / lengths [B,K], updated in place as by las_beam_step;
+ *   records    word_ids / parent_ids [B*K, >= t + 1] int32 with row stride ld_rec: COLUMN t receives the chosen word and the
+ *              beam it extends; next_token (nullable: the last step) [B*K, >= t + 2] with row stride ld_tok: column t + 1
+ *              receives the word (the token fed to step t + 1);
+ *   feed       x_next (nullable): the embedded word emb[word][0, emb_cols) (bf16 table, row stride ld_emb) into row b*K + j of
+ *              x_next (row stride ldx elements): the first columns of the next step's operand row;
+ *   gathers    njobs <= LAS_BEAM_MAX_JOBS row gathers, done BEFORE the feed: row b*K + j of a job (row_bytes bytes at
+ *              base + (b*K + j) * row_stride) becomes what row b*K + parent_ids[b, j] held; bytes between the rows are not
+ *              touched.  The decoder state the surviving beams continue from;
+ *   ledger     utt_done [B] (0 at the start), *remaining (B at the start), *steps_done (0 at the start): the workgroup whose
+ *              utterance first has all K beams finished takes one off *remaining; the one that takes it to 0 writes
+ *              *steps_done = t + 1.
+ * Freeze: a launch with 0 < *steps_done <= t (the search ended in an earlier launch: *remaining == 0) writes NOTHING, so
+ * steps enqueued on the stream past the end of the search leave the state, the records and the gather targets as they were. */
+enum { LAS_BEAM_MAX_WIDTH = 32, LAS_BEAM_MAX_JOBS = 16 };
+typedef struct las_beam_gather_job {
+  void* base;
+  int64_t row_stride, row_bytes;
+} las_beam_gather_job;
+typedef struct las_beam_adv {
+  int32_t B, K, V, eos, t, njobs;
+  const float* logits;
+  int64_t ldl;
+  float* log_probs;
+  int32_t* finished;
+  int32_t* lengths;
+  int32_t* word_ids;
+  int32_t* parent_ids;
+  int64_t ld_rec;
+  int32_t* next_token;
+  int64_t ld_tok;
+  const las_bf16* emb;
+  int64_t ld_emb;
+  las_bf16* x_next;
+  int64_t ldx;
+  int32_t emb_cols, reserved;
+  int32_t* utt_done;
+  int32_t* remaining;
+  int32_t* steps_done;
+  las_beam_gather_job jobs[LAS_BEAM_MAX_JOBS];
+} las_beam_adv;
+int las_beam_advance(const las_beam_adv* args, void* stream);
+/* tf.contrib.seq2seq.gather_tree on the records of las_beam_advance: out [B, n, K] int32, out[b, :, k] = final beam k of
+ * utterance b backtracked through parent_ids from step min(max_k lengths[b, k], n) - 1; everything at or past that length and
+ * everything after a beam's first eos is eos.  The records are read at columns [col0, col0 + n) (col0: the partial-target
+ * prefix). */
+int las_beam_gather_tree(const int32_t* word_ids, const int32_t* parent_ids, int64_t ld_rec, int col0, int n,
+                         const int32_t* lengths, int B, int K, int eos, int32_t* out, void* stream);
+
 /* sequence_loss_sigmoid / compute_loss_sigmoid of the sigmoid-output decoder (--binary_outputs without
  * --binf_projection; model_helper.py:81-95,98-130): logits [B*U rows, row stride ldl] fp32 over nf binary features,
  * targets bf16 0/1 rows (row stride ldt), seq_len [B] = the weights' sequence_mask lengths (TRAIN: target lengths; EVAL:

@@ -124,6 +124,8 @@ _SIGS = {
     'las_decoder_persist2_bwd_supported': ([_i32, _i32, _i32, _i32, _i32, _i32], C.c_int),
     'las_decoder_persist_bwd': ([_vp, _vp], C.c_int),
     'las_beam_step': ([_vp, _i64, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp], C.c_int),
+    'las_beam_advance': ([_vp, _vp], C.c_int),
+    'las_beam_gather_tree': ([_vp, _vp, _i64, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp], C.c_int),
     'las_log_probs_loss': ([_vp, _i64, C.c_int, C.c_int, _f32, _f32, _vp, _vp, _i64, _vp], C.c_int),
     'las_normal_fill': ([_vp, _i64, C.c_uint32, C.c_uint32, _vp], C.c_int),
     'las_relu_bf16': ([_vp, _i64, _vp], C.c_int),
@@ -204,6 +206,33 @@ class DecPersistBwd(C.Structure):
         ('k1c', _vp), ('ldk1', _i64), ('W1', _i32), ('wiring', _i32), ('gates1', _vp), ('c1', _vp), ('dz1', _vp), ('dc1', _vp),
         ('dfeed1_all', _vp), ('d_out1', _vp), ('ld_dout1', _i64), ('inc_dout1', _i64), ('win0', _i32), ('win1', _i32),
         ('in_stream0', C.c_uint32), ('in_stream1', C.c_uint32)]
+
+
+BEAM_MAX_WIDTH, BEAM_MAX_JOBS = 32, 16
+
+
+class BeamGatherJob(C.Structure):
+    """struct las_beam_gather_job (include/las_hip.h): rows of row_bytes bytes, row_stride bytes apart."""
+    _fields_ = [('base', _vp), ('row_stride', _i64), ('row_bytes', _i64)]
+
+
+class BeamAdv(C.Structure):
+    """struct las_beam_adv (include/las_hip.h)."""
+    _fields_ = [('B', _i32), ('K', _i32), ('V', _i32), ('eos', _i32), ('t', _i32), ('njobs', _i32),
+                ('logits', _vp), ('ldl', _i64), ('log_probs', _vp), ('finished', _vp), ('lengths', _vp),
+                ('word_ids', _vp), ('parent_ids', _vp), ('ld_rec', _i64), ('next_token', _vp), ('ld_tok', _i64),
+                ('emb', _vp), ('ld_emb', _i64), ('x_next', _vp), ('ldx', _i64), ('emb_cols', _i32), ('reserved', _i32),
+                ('utt_done', _vp), ('remaining', _vp), ('steps_done', _vp), ('jobs', BeamGatherJob * BEAM_MAX_JOBS)]
+
+    def set_jobs(self, rows):
+        """rows: 2-D views [B*K, width] with unit inner stride -- one gather job each."""
+        if len(rows) > BEAM_MAX_JOBS:
+            raise LasError('beam advance: %d gather jobs (at most %d)' % (len(rows), BEAM_MAX_JOBS))
+        for i, r in enumerate(rows):
+            if r.dim() != 2 or r.stride(1) != 1:
+                raise LasError('beam advance: a gather job is a 2-D view with unit inner stride')
+            self.jobs[i] = BeamGatherJob(r.data_ptr(), r.stride(0) * r.element_size(), r.shape[1] * r.element_size())
+        self.njobs = len(rows)
 
 
 ATT_LUONG, ATT_BAHDANAU, ATT_CUSTOM, ATT_LUONG_MONOTONIC, ATT_BAHDANAU_MONOTONIC = 0, 1, 2, 3, 4

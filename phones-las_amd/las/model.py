@@ -680,6 +680,10 @@ def greedy_persist_enabled(B, max_iterations):
 
 
 GREEDY_WINDOW = 32      # steps per launch of the one-launch greedy decode (LAS_DEC_GREEDY_WINDOW overrides)
+BEAM_WINDOW = 32        # decoder steps enqueued per read of the device beam search's ledger (LAS_BEAM_WINDOW overrides)
+# Beam search without LAS_BEAM_HOST set.  False: the host loop, until the device route has been run and timed on an MI355X
+# (scripts/gpu_beam_rate.py); LAS_BEAM_HOST=0 takes the device route meanwhile.
+BEAM_DEVICE_DEFAULT = False
 
 
 def run_greedy_windows(p, B, U, V, Vp, eos_id, dev, flops_per_step):

@@ -1108,6 +1108,119 @@ class GeneralSpeller:
         return self.forward_greedy(memory, mem_len, encoder_state, max_iterations, beam_width=beam_width,
                                    partial_targets=partial_targets)
 
+    def _beam_device_ok(self, K):
+        """The device route of the beam search (las_beam_advance + las_beam_gather_tree).  LAS_BEAM_HOST, read at every call:
+        '1' takes the token-by-token loop of forward_greedy (the yardstick), '0' the device route, unset the default
+        (model.BEAM_DEVICE_DEFAULT).  A beam wider than the kernel's cap, or a decoder with more state rows to gather than one
+        launch takes (two per cell, one more for a monotonic attention), keeps the loop."""
+        from .model import BEAM_DEVICE_DEFAULT
+        v = os.environ.get('LAS_BEAM_HOST', '')
+        if v == '1' or (v != '0' and not BEAM_DEVICE_DEFAULT):
+            return False
+        return K <= hip.BEAM_MAX_WIDTH and 2 * self.NL + (1 if self.mono else 0) <= hip.BEAM_MAX_JOBS
+
+    def _beam_device_loop(self, sv, att, qc, z, logits, fed, samples, parents, state, prefix, L, S, B0, K):
+        """forward_greedy's beam loop with nothing between the steps on the host: per step the cell GEMMs and cell kernels (h
+        straight into the next operand row), the attention (its [query | context] row written by the kernel), the attention-layer
+        and projection GEMMs, and ONE las_beam_advance, which does what the host loop does with a dozen torch launches -- records,
+        fed token, embedded feed, the parent gather of X / c / alignment -- and keeps the count of unfinished utterances.  Steps are
+        enqueued in windows of BEAM_WINDOW (LAS_BEAM_WINDOW overrides; prefix steps count) and the host reads (remaining,
+        steps_done) once per window; a launch past the end of the search finds it over and writes nothing, so the beam state at
+        the read is the state at the end whatever the window.  The backtracking is las_beam_gather_tree.  Operands: those
+        forward_greedy built."""
+        from .model import BEAM_WINDOW
+        d = self.hp
+        B, U = sv['B'], sv['U']
+        Hd, V, Vp, A, NL, M = self.Hd, self.Vo, self.Vop, self.A, self.NL, self.M
+        dev, i32 = logits.device, torch.int32
+        lib, st = hip.lib(), hip.stream()
+        X, h, cs = sv['X'], sv['h'], sv['cs']
+        b_lp, b_fin, b_len = state
+        qlayer = 0 if self.bottom else NL - 1
+        w = int(os.environ.get('LAS_BEAM_WINDOW', '0') or 0)
+        w = max(1, w if w > 0 else BEAM_WINDOW)
+        ledger = torch.zeros(B0 + 2, dtype=i32, device=dev)           # utt_done [B0] | remaining | steps_done
+        ledger[B0] = B0
+        if L > 0 and L < S:
+            fed[:, L] = prefix[:, 0]                                   # start_tokens of the search
+        if self.tokx:                                                  # the tokens known before the search: <s> / the prefix
+            n0 = min(L + 1, S)
+            X[0][:, :n0, :self.Ep] = self.emb_bf[fed[:, :n0].long()]
+        a = hip.BeamAdv()
+        a.B, a.K, a.V, a.eos = B0, K, V, d.eos_id
+        a.ldl = U * Vp
+        a.log_probs, a.finished, a.lengths = hip.addr(b_lp), hip.addr(b_fin), hip.addr(b_len)
+        a.word_ids, a.parent_ids, a.ld_rec = hip.addr(samples), hip.addr(parents), U
+        a.ld_tok = fed.stride(0)
+        a.utt_done, a.remaining, a.steps_done = hip.addr(ledger), hip.addr(ledger, B0), hip.addr(ledger, B0 + 1)
+        if self.tokx:
+            a.emb, a.ld_emb, a.emb_cols, a.ldx = hip.addr(self.emb_bf), self.Ep, self.Ep, U * (self.win[0] + Hd)
+        launches = syncs = 0
+        t0, done, steps_done = 0, False, 0
+        while t0 < S and not done:
+            t1 = min(t0 + w, S)
+            for t in range(t0, t1):
+                last = t + 1 == S
+
+                def run_cell(l):
+                    Kl = self.win[l] + Hd
+                    hip.gemm_nt(X[l][:, t], self.kT[l], z, B, 4 * Hd, Kl, lda=U * Kl, ldb=Kl, ldc=4 * Hd)
+                    self._cell_fwd(l, t, sv, z, hip.addr(fed, t), fed.stride(0),
+                                   h2=None if last else (hip.addr(X[l], (t + 1) * Kl + self.win[l]), U * Kl))
+
+                run_cell(0)
+                if not self.bottom:
+                    for l in range(1, NL):
+                        X[l][:, t, :Hd].copy_(h[l - 1][:, t])
+                        run_cell(l)
+                self._attention_fwd(t, sv, hip.addr(h[qlayer], t * Hd), U * Hd,
+                                    qc=(hip.addr(qc, t * (Hd + M)), U * (Hd + M)) if self.has_al else None)
+                if self.has_al:
+                    hip.gemm_nt(qc[:, t], self.walT, att[:, t], B, A, Hd + M, lda=U * (Hd + M), ldb=Hd + M, ldc=U * A, out_bf16=True)
+                if self.bottom:
+                    for l in range(1, NL):
+                        wc = A if l == 1 else Hd
+                        X[l][:, t, :wc].copy_(att[:, t] if l == 1 else h[l - 1][:, t])
+                        run_cell(l)
+                if not last:
+                    X[0][:, t + 1, self.T0:self.T0 + A].copy_(att[:, t])
+                    if self.bottom:
+                        for l in range(1, NL):
+                            wc = A if l == 1 else Hd
+                            X[l][:, t + 1, wc:wc + A].copy_(att[:, t])
+                if t < L:                   # prefix step: only the state moves on
+                    continue
+                out_t = h[NL - 1][:, t] if (self.bottom and NL > 1) else att[:, t]
+                hip.gemm_nt(out_t, self.wprojT, logits[:, t], B, Vp, self.P, lda=out_t.stride(0), ldb=self.P, ldc=U * Vp,
+                            bias=self.bproj)
+                a.t, a.logits = t, hip.addr(logits, t * Vp)
+                if last:
+                    a.next_token, a.x_next, a.njobs = 0, 0, 0
+                else:                       # the surviving beams continue from their parents' decoder state
+                    a.next_token = hip.addr(fed)
+                    if self.tokx:
+                        a.x_next = hip.addr(X[0], (t + 1) * (self.win[0] + Hd))
+                    rows = []
+                    for l in range(NL):
+                        rows += [X[l][:, t + 1], cs[l][:, t + 1]]
+                    if self.mono:
+                        rows.append(sv['align'][:, t])
+                    a.set_jobs(rows)
+                hip.check(lib.las_beam_advance(C.byref(a), st))
+                launches += 1
+            remaining, steps_done = ledger[B0:].tolist()               # the one synchronisation of the window
+            syncs += 1
+            done = remaining == 0
+            t0 = t1
+        steps = steps_done if done else S
+        self.last_decode_route, self.last_decode_launches, self.last_decode_syncs = 'beam_device', launches, syncs
+        n = max(steps - L, 0)
+        ids = torch.full((B0, n, K), d.eos_id, dtype=i32, device=dev)
+        if n > 0:
+            hip.check(lib.las_beam_gather_tree(hip.p(samples), hip.p(parents), U, L, n, hip.p(b_len), B0, K, d.eos_id,
+                                               hip.p(ids), st))
+        return ids, b_len, b_lp
+
     def forward_greedy(self, memory, mem_len, encoder_state, max_iterations, parts=4, beam_width=0, partial_targets=None):
         """GreedyEmbeddingHelper decode (las/model.py:270-274,337-347) with the general cell stack
         (beam_width > 0: see forward_beam)."""
@@ -1141,7 +1254,7 @@ class GeneralSpeller:
             L = int(prefix.shape[1])
         S = max_iterations + L
         init, _ = self._init_states(encoder_state, B)
-        self.last_decode_route, self.last_decode_launches = 'steps', 0
+        self.last_decode_route, self.last_decode_launches, self.last_decode_syncs = 'steps', 0, 0
         if K <= 0 and not binary and self._greedy_persist_ok(B, S):
             return self._forward_greedy_persist(memory, mem_len, init, S)
         ids0 = torch.full((B, 1), d.sos_id, dtype=torch.int32, device=dev)
@@ -1188,6 +1301,9 @@ class GeneralSpeller:
             b_par = torch.zeros(B0, K, dtype=i32, device=dev)
             parents = torch.zeros(B, U, dtype=i32, device=dev)
             base = (torch.arange(B0, device=dev) * K).unsqueeze(1)
+            if self._beam_device_ok(K):
+                return self._beam_device_loop(sv, att, qc, z, logits, fed, samples, parents, (b_lp, b_fin, b_len),
+                                              prefix if L > 0 else None, L, S, B0, K)
         for t in range(S):
             last = t + 1 == S
 
